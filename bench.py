@@ -24,10 +24,15 @@ replicated.
 value = whole-job algorithmic TFLOP/s (F_proj + F_qr + F_small of the global
 problem) / max-over-ranks wall time; ms_per_step = rSVD wall-clock.
 
-Extra fields: "roofline" (the dominant projection kernel, HIP-event timed on the engine's stream
-in a second pass over the same K steps; bound = min(MFMA peak, AI x 8 TB/s) with AI = 2 l /
-bytes per A element), "cpu_baseline" (the fp64 C oracle -- a restatement of the
-reference, Eigen is absent -- on rank 0 at N = 1 on a bounded sample of the same workload).
+A plain run sets up, warms up, times the K steps and prints the result line; --dump-outputs DIR
+also writes what the last timed step returned (U, S, V) as DIR/<name>.npy.
+
+--full adds everything else, each in a run of its own after the timed steps: "roofline" (the
+dominant projection kernel, HIP-event timed on the engine's stream in a second pass over the same
+K steps; bound = min(MFMA peak, AI x 8 TB/s) with AI = 2 l / bytes per A element, SURVEY.md
+§8(d)), "cpu_baseline" (the fp64 C oracle -- a restatement of the reference, Eigen is absent -- on
+rank 0 at N = 1 on a bounded sample of the same workload), "check" (the self-check of the
+outputs), "lowp_intermediates" (the opt-in variant) and C1's known answers and CPU latencies.
 """
 from __future__ import annotations
 
@@ -261,6 +266,36 @@ def self_check(torch, dist, A, a_scale, U, S, V, world, k_top=32):
     return {"top_k": k, "max_ritz_residual": rel, "V_orth_err": vo, "ok": bool(rel < 1e-2 and vo < 1e-2)}
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: upper bound of everything one run writes
+
+
+def sample_rows(torch, X, max_bytes, seed):
+    """X as float32 / float64 on the host; when it is larger than max_bytes, a fixed sample of its
+    rows (ascending indices drawn once from `seed`, every column kept)."""
+    import numpy as np
+
+    X = X if X.dtype == torch.float64 else X.float()
+    row_bytes = max(1, X[0].numel() * X.element_size()) if X.dim() > 1 else X.element_size()
+    keep = max(1, max_bytes // row_bytes)
+    if keep < X.shape[0]:
+        idx = np.sort(np.random.default_rng(seed).choice(X.shape[0], size=keep, replace=False))
+        X = X[torch.from_numpy(idx).to(X.device)]
+    return np.ascontiguousarray(X.cpu().numpy())
+
+
+def dump_outputs(torch, path, U, S, V, rank, world):
+    """--dump-outputs: the (U, S, V) the last timed step returned.  U is row-sharded (every rank
+    writes its rows, U_rank<r>.npy at N > 1); S and V are replicated (rank 0 writes them)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BYTES - S.numel() * 8) // (2 * world)  # U of every rank, V once: below DUMP_BYTES in all
+    np.save(os.path.join(path, "U.npy" if world == 1 else f"U_rank{rank}.npy"), sample_rows(torch, U, share, 0x5EED0003))
+    if rank == 0:
+        np.save(os.path.join(path, "S.npy"), sample_rows(torch, S, DUMP_BYTES, 0))
+        np.save(os.path.join(path, "V.npy"), sample_rows(torch, V, share, 0x5EED0004))
+
+
 def launch_ranks(n):
     """Run this script as N ranks under torch.distributed.run (a child process: nothing in this
     process has initialised the GPU, and it is never replaced by exec)."""
@@ -289,7 +324,13 @@ def main():
     ap.add_argument("--l", type=int, default=None)
     ap.add_argument("--q", type=int, default=None)
     ap.add_argument("--dtype", default=None, choices=["f32", "f64", "bf16", "fp8"])
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-oracle work (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline pass, the lowp-intermediates variant, the "
+                         "self-check of the outputs, the CPU-oracle baseline and C1's extras (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the U, S, V of the last timed step as DIR/<name>.npy (float32 / float64; a fixed "
+                         "seeded row sample of U and V where they exceed the 64 MB the dump may take)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU-oracle work (0 = skip)")
     ap.add_argument("--comm", default="library", choices=["library", "torch"],
                     help="N > 1: the handle's own RCCL communicator (rsvd_comm_init) or torch.distributed hooks")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -380,17 +421,20 @@ def main():
     def step():
         return eng.rsvd(A, l, q=q, seed=0x5EED0002, a_scale=a_scale, check_errors=False)
 
+    last = None
     for _ in range(args.warmup):
-        step()
+        last = step()  # held as the timed loop holds it: both output sets are allocated before the clock starts
     torch.cuda.synchronize()
+    del last
 
     def timed(k):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None
         for _ in range(k):
-            step()
+            last = step()
         eng.sync()  # device-side failures of any of the K runs raise here (rsvd_sync)
         torch.cuda.synchronize()
         if world > 1:
@@ -400,9 +444,70 @@ def main():
             t = torch.tensor([dt_s], device="cuda", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_s = float(t.item())
-        return dt_s
+        return dt_s, last
 
-    elapsed = timed(args.steps)
+    elapsed, last = timed(args.steps)
+    if args.dump_outputs and last is not None:
+        dump_outputs(torch, args.dump_outputs, *last, rank, world)
+    del last
+
+    f_proj, f_qr, f_small = algorithmic_flops(m_local if emu else m_global, n, l, q)
+    f_total = f_proj + f_qr + f_small
+    ms_per_step = elapsed / args.steps * 1e3
+    value = f_total * args.steps / elapsed / 1e12
+
+    def emit(info, **extras):
+        """Rank 0 prints the result line (the headline fields, then what --full added)."""
+        if rank != 0:
+            return
+        par = "single-gpu" if world == 1 else (f"row-partition x{world}" if strong else f"row-shard x{world}")
+        if emu:
+            par = (f"EMULATED rank 0 of {emu} on one GPU (no-op collectives; n shard {info.get('n_shard_rows')} "
+                   f"rows): per-rank kernel time only, not an N-GPU measurement")
+        if world > 1 and info.get("n_shard_rows"):
+            par += f", n side sharded ({info['n_shard_rows']} rows/GPU)"
+        if world > 1:
+            par += (", gloo via torch.distributed hooks (test mode)" if args.backend == "gloo" else
+                    ", RCCL " + ("owned by the C ABI (rsvd_comm_init)" if args.comm == "library" else "via torch.distributed hooks"))
+        line = {
+            "metric": "rSVD wall-clock + achieved TFLOP/s, dense m x n rank-k",
+            "value": value,
+            "unit": "TFLOP/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": dt,
+            "data": "synthetic",
+            "config": {
+                "workload": label + (f"; {m_global}x{n} global, {m_local} rows/GPU" if world > 1 else ""),
+                "m": m_global, "n": n, "l": l, "q": q, "m_per_gpu": m_local,
+                "lda": int(A.stride(1)) if A.dim() == 2 else m_local,
+                "parallelism": par,
+                "algorithmic_tflop_per_step": f_total / 1e12,
+            },
+            "full": bool(args.full),
+            "engine_info": info,
+        }
+        line.update(extras)
+        print(json.dumps(line), flush=True)
+
+    def finish():
+        eng.close()  # releases the handle's RCCL communicator (rsvd_destroy)
+        if world > 1:
+            dist.destroy_process_group()
+        if os.environ.get("RSVD_MAPS_OUT"):  # diagnostics: the process's mappings, to symbolise an exit-time fault
+            with open("/proc/self/maps") as f, open(os.environ["RSVD_MAPS_OUT"], "w") as g:
+                g.write(f.read())
+
+    if not args.full:  # the plain run ends here: the headline alone
+        emit(eng.info())
+        finish()
+        return
+
     # opt-in variant (not the headline): RSVD_FLAG_LOWP_INTERMEDIATES, power iterations before the last on
     # the bf16 operand alone (include/rsvd_c.h; its accuracy depends on the spectrum's decay)
     fast = None
@@ -439,10 +544,6 @@ def main():
         check = self_check(torch, dist, A, a_scale, U_, S_, V_, world)
         del U_, S_, V_
 
-    f_proj, f_qr, f_small = algorithmic_flops(m_local if emu else m_global, n, l, q)
-    f_total = f_proj + f_qr + f_small
-    ms_per_step = elapsed / args.steps * 1e3
-    value = f_total * args.steps / elapsed / 1e12
     if fast:
         fast["value_tflops"] = f_total / (fast["ms_per_step"] * 1e-3) / 1e12
 
@@ -541,51 +642,11 @@ def main():
 
     c1 = c1_extras(torch, R, eng, A, q, max(args.cpu_budget, 3.0)) if args.config == "c1" and rank == 0 else None
 
-    if rank == 0:
-        par = "single-gpu" if world == 1 else (f"row-partition x{world}" if strong else f"row-shard x{world}")
-        if emu:
-            par = (f"EMULATED rank 0 of {emu} on one GPU (no-op collectives; n shard {info.get('n_shard_rows')} "
-                   f"rows): per-rank kernel time only, not an N-GPU measurement")
-        if world > 1 and info.get("n_shard_rows"):
-            par += f", n side sharded ({info['n_shard_rows']} rows/GPU)"
-        if world > 1:
-            par += (", gloo via torch.distributed hooks (test mode)" if args.backend == "gloo" else
-                    ", RCCL " + ("owned by the C ABI (rsvd_comm_init)" if args.comm == "library" else "via torch.distributed hooks"))
-        line = {
-            "metric": "rSVD wall-clock + achieved TFLOP/s, dense m x n rank-k",
-            "value": value,
-            "unit": "TFLOP/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": dt,
-            "data": "synthetic",
-            "config": {
-                "workload": label + (f"; {m_global}x{n} global, {m_local} rows/GPU" if world > 1 else ""),
-                "m": m_global, "n": n, "l": l, "q": q, "m_per_gpu": m_local,
-                "lda": int(A.stride(1)) if A.dim() == 2 else m_local,
-                "parallelism": par,
-                "algorithmic_tflop_per_step": f_total / 1e12,
-            },
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "engine_info": info,
-            "check": check,
-            "lowp_intermediates": fast,
-        }
-        if c1 is not None:
-            line["c1"] = c1
-        print(json.dumps(line), flush=True)
-    eng.close()  # releases the handle's RCCL communicator (rsvd_destroy)
-    if world > 1:
-        dist.destroy_process_group()
-    if os.environ.get("RSVD_MAPS_OUT"):  # diagnostics: the process's mappings, to symbolise an exit-time fault
-        with open("/proc/self/maps") as f, open(os.environ["RSVD_MAPS_OUT"], "w") as g:
-            g.write(f.read())
+    extras = {"roofline": roof, "cpu_baseline": cpu, "check": check, "lowp_intermediates": fast}
+    if c1 is not None:
+        extras["c1"] = c1
+    emit(info, **extras)
+    finish()
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
-"""Generate the committed golden fixtures under tests/golden/ (run here, where /root/reference is
-mounted; the fixtures travel, the reference does not).
+"""Generate the committed golden fixtures under tests/golden/ (the fixtures travel with the
+repository, the reference does not).
 
 * inputs.npz   -- the reference's own committed test inputs as dense float64 matrices:
                   input/sparse_matrix{,100,110,140,160}.mtx (tests/rSVD_test.cpp, svd_test.cpp)
@@ -11,13 +11,16 @@ mounted; the fixtures travel, the reference does not).
                   process_matrix() (test_run_rSVD.py:41-57: np.linalg.svd; test_run_QR.py:25-40:
                   np.linalg.qr mode="reduced") writes U, diag(S), V^T and Q, R as MatrixMarket files
                   (%.18e, exact for doubles), which are read back here: singular values, the
-                  well-determined leading singular vectors, and |diag R|.  Only in this build
-                  container (the reference never travels); nothing of its code is kept.
+                  well-determined leading singular vectors, and |diag R|.  Nothing of its code is
+                  kept.  Without a reference tree the same two LAPACK calls are made here on the
+                  matrices of the committed inputs.npz (lapack_outputs()); both routes write the
+                  same bytes.
 * philox.npz   -- the first Gaussian draws of the Philox4x32-10 + Box-Muller stream the engine
                   and the oracle share (generated here by a pure-Python restatement, independent
                   of both C implementations).
 
-Usage:  python tests/golden/make_golden.py [/root/reference [out_dir]]
+Usage:  python tests/golden/make_golden.py [out_dir [reference_dir]]
+        (no reference_dir: the inputs are the committed inputs.npz, see lapack.npz above)
 """
 import math
 import os
@@ -88,20 +91,37 @@ def reference_outputs(ref, paths):
         shutil.rmtree(scratch, ignore_errors=True)
 
 
+def lapack_outputs(files):
+    """What reference_outputs() returns, from the dense inputs alone: numpy's LAPACK SVD and reduced
+    QR, the two calls the reference's scripts make.  Adding 0.0 turns -0.0 into +0.0, as the
+    MatrixMarket round trip of the reference's route does (scipy's reader sums the entries into a
+    zero matrix)."""
+    out = {}
+    for key, A in files.items():
+        U, S, VT = np.linalg.svd(A)
+        Q, R = np.linalg.qr(A, mode="reduced")
+        out[key] = (U + 0.0, S + 0.0, VT + 0.0, Q + 0.0, R + 0.0)
+    return out
+
+
 def main():
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
-    out_dir = sys.argv[2] if len(sys.argv) > 2 else HERE
+    out_dir = sys.argv[1] if len(sys.argv) > 1 else HERE
+    ref = sys.argv[2] if len(sys.argv) > 2 else None
     files, paths = {}, {}
-    for sub in ("input", os.path.join("image_compression", "data", "input", "mat")):
-        d = os.path.join(ref, sub)
-        for f in sorted(os.listdir(d)):
-            if f.endswith(".mtx"):
-                key = os.path.splitext(f)[0]
-                files[key] = np.asarray(mmread(os.path.join(d, f)).toarray(), dtype=np.float64)
-                paths[key] = os.path.join(d, f)
+    if ref is None:
+        with np.load(os.path.join(HERE, "inputs.npz")) as committed:
+            files = {key: committed[key] for key in committed.files}
+    else:
+        for sub in ("input", os.path.join("image_compression", "data", "input", "mat")):
+            d = os.path.join(ref, sub)
+            for f in sorted(os.listdir(d)):
+                if f.endswith(".mtx"):
+                    key = os.path.splitext(f)[0]
+                    files[key] = np.asarray(mmread(os.path.join(d, f)).toarray(), dtype=np.float64)
+                    paths[key] = os.path.join(d, f)
     np.savez_compressed(os.path.join(out_dir, "inputs.npz"), **files)
 
-    refout = reference_outputs(ref, paths)
+    refout = lapack_outputs(files) if ref is None else reference_outputs(ref, paths)
     gold = {}
     for key, A in files.items():
         U, S, VT, Q, R = refout[key]

@@ -46,6 +46,34 @@ def test_committed_evidence_lookups():
     assert mb2 is not None and mb2["bound"] == "lower" and mb2["clock_GHz"] is None and 0.3 < mb2["frac"] < 1.0
 
 
+def test_dump_outputs_bounded_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs (host tensors here): float32 / float64 files, every column kept, a fixed
+    ascending row sample where U or V exceed their share of the bound, the same rows on every call."""
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(0)
+    U = torch.randn(1000, 8, generator=g).t().contiguous().t()  # column-major, as the engine returns it
+    S = torch.rand(8, generator=g)
+    V = torch.randn(50, 8, generator=g, dtype=torch.float64)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 8 + 2 * 100 * 8 * 4)  # S, then 100 fp32 rows each for U and V
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / d), U, S, V, 0, 1)
+    got = {f: np.load(tmp_path / "a" / f"{f}.npy") for f in "USV"}
+    assert got["U"].dtype == np.float32 and got["S"].dtype == np.float32 and got["V"].dtype == np.float64
+    assert got["U"].shape == (100, 8) and got["S"].shape == (8,) and got["V"].shape == (50, 8)
+    assert sum(os.path.getsize(tmp_path / "a" / f"{f}.npy") for f in "USV") <= 8 * 8 + 2 * 100 * 8 * 4 + 3 * 128
+    assert np.array_equal(got["S"], S.numpy()) and np.array_equal(got["V"], V.numpy())
+    # the sampled rows are rows of U, in ascending order
+    rows = [int(np.flatnonzero((U.numpy() == r).all(1))[0]) for r in got["U"]]
+    assert rows == sorted(rows) and len(set(rows)) == 100
+    for f in "USV":
+        assert np.array_equal(got[f], np.load(tmp_path / "b" / f"{f}.npy"))
+    # N > 1: every rank writes its U shard, rank 0 alone S and V
+    bench.dump_outputs(torch, str(tmp_path / "c"), U, S, V, 1, 2)
+    assert sorted(os.listdir(tmp_path / "c")) == ["U_rank1.npy"]
+
+
 def test_self_launch_builds_torchrun_command(monkeypatch):
     """`python bench.py --gpus N` starts its own N ranks: torch.distributed.run
     with one process per GPU on 127.0.0.1, the bench's flags carried in RSVD_BENCH_ARGV (torchrun's

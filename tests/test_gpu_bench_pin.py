@@ -4,7 +4,7 @@ bench.py times C4 on bench.make_A (128 directions at 0.9^t plus 1e-3 Gaussian no
 same generator builds a 16384 x 16384 A -- a quarter of C4's side, the largest the fp64 CPU oracle
 finishes in well under a minute on the box's host cores -- and the engine's rSVD (l = 256, q = 2,
 the bench's seed, hence the same bf16 Omega) is compared with the oracle's
-(/root/reference/src/rSVD.cpp:72-133 restated in oracle/rsvd_oracle.c) on the bf16-rounded A:
+(the reference's src/rSVD.cpp:72-133 restated in oracle/rsvd_oracle.c) on the bf16-rounded A:
 * S: relative Frobenius <= 1e-4 (north_star);
 * U, V: sign-aligned relative Frobenius <= 1e-4 over the triplets with s_i >= 10 s_l (the
   noise-cluster triplets below that are not determined by the data to 1e-4 and are not compared).

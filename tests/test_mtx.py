@@ -1,6 +1,6 @@
 """MatrixMarket I/O (rsvd_kamaneh_raganato_terrana_amd/mtx.py) and the reference harness mirror
 (tools/rsvd_test.py): the inputs it regenerates equal the reference's input/*.mtx (compared
-here when the reference tree is present), reads agree with the oracle's reader, writes round-trip
+here with their dense copies in tests/golden/inputs.npz), reads agree with the oracle's reader, writes round-trip
 exactly.  GPU: the harness reproduces the known answers of SURVEY.md §8c on those inputs."""
 import os
 import sys
@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import REPO
+from conftest import GOLDEN, REPO
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
@@ -16,7 +16,7 @@ import oracle  # noqa: E402  (test infrastructure)
 import rsvd_test  # noqa: E402
 from rsvd_kamaneh_raganato_terrana_amd.mtx import read_market, write_market  # noqa: E402
 
-REF_INPUT = "/root/reference/input"
+REF_INPUT = ("sparse_matrix", "sparse_matrix100", "sparse_matrix110", "sparse_matrix140", "sparse_matrix160")
 
 
 @pytest.fixture(scope="module")
@@ -42,12 +42,12 @@ def test_reader_agrees_with_oracle_reader(inputs):
         assert np.array_equal(read_market(p), oracle.read_matrix_market(p))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INPUT), reason="reference tree absent")
 def test_generated_inputs_equal_reference_files(inputs):
-    for name in sorted(os.listdir(REF_INPUT)):
-        ours = read_market(os.path.join(inputs, name))
-        ref = read_market(os.path.join(REF_INPUT, name))
-        assert np.array_equal(ours, ref), name
+    """The reference's input/*.mtx travel as dense matrices in tests/golden/inputs.npz."""
+    ref = np.load(os.path.join(GOLDEN, "inputs.npz"))
+    for name in REF_INPUT:
+        ours = read_market(os.path.join(inputs, name + ".mtx"))
+        assert np.array_equal(ours, ref[name]), name
 
 
 def test_write_read_round_trip(tmp_path):

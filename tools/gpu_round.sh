@@ -9,8 +9,10 @@ mkdir -p gpurun_out
 if [ "$mode" = tests ]; then
   tools/gpu_tests.sh ${TESTS:-tests} || exit 1
 fi
-timeout -k 10 300 python3 bench.py > gpurun_out/bench_${tag}.json 2> gpurun_out/bench_${tag}.err || { tail -20 gpurun_out/bench_${tag}.err; exit 1; }
-cat gpurun_out/bench_${tag}.json
+out=${OUT:-bench_out}  # the full bench record (roofline, CPU baseline, self-check)
+mkdir -p $out
+timeout -k 10 300 python3 bench.py --full > $out/bench_${tag}.json 2> $out/bench_${tag}.err || { tail -20 $out/bench_${tag}.err; exit 1; }
+cat $out/bench_${tag}.json
 tools/prof_cfg.sh c4 3 || exit 1
 cp gpurun_out/prof_c4.txt gpurun_out/prof_c4_${tag}.txt
 if [ -x tools/fetch_calib ]; then
