@@ -339,7 +339,9 @@ class Engine:
             self.sync()
         return U, S, V
 
-    def range_finder(self, A, omega, q: int = 2, qr_mode: int = QRMode.Auto):
+    def range_finder(self, A, omega, q: int = 2, qr_mode: int = QRMode.Auto, out=None):
+        """Device intermediate_step: the orthonormal range basis Q (m x l).  out: a column-major
+        m x l tensor to write Q into (any leading dimension >= m), as rsvd's out=."""
         A, _ = colmajor(A)
         odt = self.out_dtype(A.dtype)
         om, ldo = colmajor(omega.to(device=A.device, dtype=odt))
@@ -347,7 +349,9 @@ class Engine:
         d = self.desc(A, l, q, SVDMethod.Jacobi, 0, qr_mode)
         self.reserve(d)
         self._bind_stream()
-        Q = empty_colmajor(A.shape[0], l, odt, A.device)
+        Q = empty_colmajor(A.shape[0], l, odt, A.device) if out is None else out
+        if Q.shape != (A.shape[0], l) or Q.dtype != odt or Q.stride(0) != 1 or Q.stride(1) < A.shape[0]:
+            raise ValueError("out must be a column-major m x l matrix of the result dtype")
         check(lib().rsvd_range_finder(self.h, ctypes.byref(d), ctypes.c_void_p(A.data_ptr()),
                                       ctypes.c_void_p(om.data_ptr()), ldo, ctypes.c_void_p(Q.data_ptr()),
                                       Q.stride(1)), self.h)
