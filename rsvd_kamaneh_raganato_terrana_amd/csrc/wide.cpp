@@ -120,7 +120,7 @@ struct WideLayout {
         off_Qh = take(bm);
         off_Ql = take(bm);
         // e4m3 A: the sketch Omega as an e4m3 panel (the fp8-MFMA sketch product, launch_wproj_s8)
-        s8 = d->dtype == RSVD_FP8_E4M3 && wproj_s8_supported(wnn, LP);
+        s8 = d->dtype == RSVD_FP8_E4M3 && wproj_s8_supported(wnn);
         off_X8 = take(s8 ? (size_t)npad * LP : 0);
         off_pslab = take(sizeof(T) * std::max<int64_t>(pslab, 1) * LP);
         off_gslab = take(sizeof(double) * gslab);
@@ -287,8 +287,8 @@ struct WideEngine {
         RSVD_TRY(ev_begin(kind, ev));
         hipEvent_t done = ev >= 0 ? h->ev_pool[ev + 1] : nullptr;
         if (L.lowp) {
-            RSVD_CK(launch_wproj(1, dtype == RSVD_FP8_E4M3, A, lda, L.m, L.n, xh, xl, L.LP, L.wnn,
-                                 reinterpret_cast<float*>(pslab), reinterpret_cast<float*>(Y), s, done));
+            RSVD_CK(launch_wproj(A, lda, L.m, L.n, xh, xl, L.wnn, reinterpret_cast<float*>(pslab),
+                                 reinterpret_cast<float*>(Y), s, done));
         } else {
             RSVD_CK(launch_proj_nn<T>(reinterpret_cast<const T*>(A), lda, L.m, L.n, X, L.LP, L.pnn, pslab, Y, s, done));
         }
@@ -299,7 +299,7 @@ struct WideEngine {
         int ev;
         RSVD_TRY(ev_begin(2, ev));
         hipEvent_t done = ev >= 0 ? h->ev_pool[ev + 1] : nullptr;
-        RSVD_CK(launch_wproj_s8(A, lda, L.m, L.n, X8, L.LP, L.wnn, reinterpret_cast<float*>(pslab),
+        RSVD_CK(launch_wproj_s8(A, lda, L.m, L.n, X8, L.wnn, reinterpret_cast<float*>(pslab),
                                 reinterpret_cast<float*>(Y), s, done));
         return RSVD_OK;
     }
@@ -309,8 +309,8 @@ struct WideEngine {
         RSVD_TRY(ev_begin(1, ev));
         hipEvent_t done = ev >= 0 ? h->ev_pool[ev + 1] : nullptr;
         if (L.lowp) {
-            RSVD_CK(launch_wproj(0, dtype == RSVD_FP8_E4M3, A, lda, L.m, L.n, qh, ql, L.LP, L.wtn,
-                                 reinterpret_cast<float*>(pslab), reinterpret_cast<float*>(Z), s, done));
+            RSVD_CK(launch_wproj(A, lda, L.m, L.n, qh, ql, L.wtn, reinterpret_cast<float*>(pslab),
+                                 reinterpret_cast<float*>(Z), s, done));
         } else {
             RSVD_CK(launch_proj_tn<T>(reinterpret_cast<const T*>(A), lda, L.m, L.n, Q, L.LP, L.ptn, pslab, Z, s, done));
         }

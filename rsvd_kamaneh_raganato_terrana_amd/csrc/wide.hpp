@@ -20,44 +20,59 @@ namespace rsvd {
 typedef uint16_t bf16_t;  // storage of one bf16
 typedef uint8_t fp8_t;    // storage of one OCP e4m3fn
 
-// ---- wide_proj.hip -----------------------------------------------------------------------------
+// ---- wide_plan.cpp (host only) / wide_proj.hip ---------------------------------------------------
+constexpr int kWprojKStep = 32;  // k per step of the bf16 / e4m3 projection kernels (one MFMA deep)
 // Sketch widths the bf16 projection kernels are built for (LP = padded l).
 bool wproj_supported_lp(int LP);
-int wproj_rows_per_block(int LP);  // output rows per workgroup (256 / 128 / 64)
-struct WProjPlan {
-    int splits;      // K splits (1 = straight into the output panel)
-    int64_t chunk;   // K range per workgroup (multiple of 32)
-    int blocks;      // output row blocks
-    bool v2;         // LDS-DMA pipelined kernel (bf16 / e4m3 A, LP >= 128, 16-B aligned columns)
-    bool ds = false; // v2 TN at LP = 128 with two k-steps per stage (128-B A runs; K a multiple of 64)
-    int tn3 = 0;      // ds with separate A / S rings (wproj3tn128_kernel): 1 = 4 A / 2 S slots, 2 = 3 / 3 (lab)
-    bool nn3 = false;  // bf16 NN at LP = 128 on wproj3_kernel (RSVD_NN3_128=0: the v2 kernel)
-    bool nn8 = false;  // e4m3 NN halves on the v3-style wproj3nn8_kernel (RSVD_NN8=0: the v2 kernel)
-    bool v3 = false; // v2 with launch-constant LDS read bases (bf16 A, LP 256 / 512; wide_proj.hip)
-    bool tn2 = false; // v3 TN at LP = 256 with two k-steps per A slot (128-B A lines)
-    bool half = false; // e4m3 A at LP = 512: two LP = 256 column-half launches (256-row tiles)
-    bool tn4 = false;  // e4m3 TN at LP 256 / 512: four k-steps per A slot (128-B A lines, wproj3tn4_kernel)
-    bool merge = false; // LP = 512 halves (half / tn4) in ONE launch, twin blocks adjacent (A from HBM once)
-    int abl = 0;      // lab-only ablations of the v3 kernel (tools/wide_lab.cpp), never set by the engine
-    int kn = -1;      // lab-only knob override of the LP = 256 v3 kernels (-1: the engine's choice)
+int wproj_rows_per_block(int LP);  // output rows per workgroup of the fallback kernel (256 / 128 / 64)
+// The kernel family a product runs on (wide_proj.hip).  The LDS-DMA families (all but Fallback) need
+// the "v2" operand layout: a 16-B aligned base, bf16 A with lda and m multiples of 8 or e4m3 A with
+// lda and m multiples of 16, and S panels zero-padded to a multiple of 32 rows (the engine allocates
+// them so).
+enum class WProjKernel {
+    Fallback,  // wproj_kernel: register-prefetched, any alignment, every LP
+    W2,        // wproj2_kernel, one k-step per stage: LP = 128, and the e4m3 NN at LP = 256
+    W2Ds,      // wproj2_kernel, two k-steps per stage: bf16 TN at LP = 128 (128-B A runs; K a multiple of 64)
+    W2Half,    // wproj2_kernel as two 256-column halves: e4m3 NN at LP = 512 (256-row tiles)
+    W3,        // wproj3_kernel, launch-constant LDS read bases: bf16 at LP 256 / 512, bf16 NN at LP = 128
+    W3Tn2,     // wproj3tn2_kernel: bf16 TN at LP = 256, two k-steps per A slot (128-B A lines)
+    W3Tn128,   // wproj3tn128_kernel: W2Ds's product on separate A / S rings
+    W3Tn4,     // wproj3tn4_kernel: e4m3 TN at LP 256 / 512, four k-steps per A slot (128-B A lines)
+    W3Nn8,     // wproj3nn8_kernel: e4m3 NN at LP = 512 as two 256-column halves
 };
-// v2 requires: a 16-B aligned base, bf16 A with lda and m multiples of 8 or e4m3 A with lda and m
-// multiples of 16, and S panels zero-padded
-// to a multiple of 32 rows (the engine allocates them so).
+const char* wproj_kernel_name(WProjKernel k);
+struct WProjPlan {
+    bool nn, fp8;  // the product the plan was made for: NN (Y = A S) or TN (Z = A^T S), bf16 or e4m3 A
+    int LP;
+    WProjKernel kernel;  // of the hi / lo product (the single-panel product: wproj_kernel_for)
+    bool merge;          // the two 256-column halves of LP = 512 in ONE launch, twin blocks adjacent (A from HBM once)
+    bool s8_scaled;      // launch_wproj_s8 takes the block-scaled K = 128 form (every stage whole), else K = 32
+    int splits;          // K splits (1 = straight into the output panel)
+    int64_t chunk;       // K range per workgroup (multiple of 32)
+    int blocks;          // output row blocks
+    // lab-only overrides (tools/wide_lab.cpp, RSVD_LAB builds), never set by the engine
+    int abl = 0;           // ablations of the W3 / W3Tn2 kernels at LP = 256
+    int kn = -1;           // knob override of the same kernels (-1: the engine's choice)
+    bool rings33 = false;  // W3Tn128 with 3 A / 3 S slots instead of 4 / 2
+};
+// Exactly the plan the engine runs; v2: the operands meet the LDS-DMA kernels' layout (above).
 WProjPlan plan_wproj(int64_t rows_out, int64_t K, int LP, bool v2 = false, bool nn = true, bool fp8 = false);
+// The kernel of one launch; split: the operand is a hi / lo panel pair (Slo != nullptr).
+WProjKernel wproj_kernel_for(const WProjPlan& p, bool split);
+// True when p.kernel is built for p's LP, nn and fp8 (launch_wproj refuses any other plan).
+bool wproj_plan_valid(const WProjPlan& p);
 // NN: Y (m x LP, fp32) = A (m x n) * S       S = n x LP bf16 panel(s)      src/rSVD.cpp:59,66
 // TN: Z (n x LP, fp32) = A^T * S             S = m x LP bf16 panel(s)      src/rSVD.cpp:63,89
-// A is column-major (lda) bf16 (a_fp8 = 0) or e4m3 (a_fp8 = 1).  Slo == nullptr: single pass.
+// A is column-major (lda), bf16 or e4m3 as the plan says.  Slo == nullptr: single pass.
 // `done` (optional) is recorded after the MFMA kernel, before the slab reduction.
-hipError_t launch_wproj(int nn, int a_fp8, const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi,
-                        const bf16_t* Slo, int LP, const WProjPlan& p, float* slabs, float* Out, hipStream_t s,
-                        hipEvent_t done = nullptr);
+hipError_t launch_wproj(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
+                        const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done = nullptr);
 
 // e4m3 A times an e4m3 panel S8 (n x LP bytes, rows zero-padded to a multiple of 32): the Gaussian
 // sketch Y = A Omega of an e4m3 A on v_mfma_f32_16x16x32_fp8_fp8 (both operands exact e4m3).
-// Needs an NN plan with v2 and LP in {256, 512} (wproj_s8_supported).
-bool wproj_s8_supported(const WProjPlan& p, int LP);
-hipError_t launch_wproj_s8(const void* A, int64_t lda, int64_t m, int64_t n, const fp8_t* S8, int LP, const WProjPlan& p,
+// Needs an e4m3 NN plan on an LDS-DMA kernel with LP in {256, 512} (wproj_s8_supported).
+bool wproj_s8_supported(const WProjPlan& p);
+hipError_t launch_wproj_s8(const void* A, int64_t lda, int64_t m, int64_t n, const fp8_t* S8, const WProjPlan& p,
                            float* slabs, float* Out, hipStream_t s, hipEvent_t done = nullptr);
 // bf16 panel holding exactly-e4m3 values -> e4m3 codes (count elements)
 hipError_t launch_bf16_to_fp8(const bf16_t* in, int64_t count, fp8_t* out, hipStream_t s);

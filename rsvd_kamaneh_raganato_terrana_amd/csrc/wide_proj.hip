@@ -21,9 +21,11 @@
 // 16 G columns (acc = 4 x G MFMA tiles).  K is split over workgroups into fp32 slabs
 // (launch_sum_slabs) when the row blocks alone cannot fill the chip; the XCD-aware remap puts
 // the row blocks of one K chunk on one XCD so their shared S chunk is an L2 hit.
+//
+// Which kernel a product runs on is the planner's choice (plan_wproj, wide_plan.cpp: host code
+// only); here each kernel family has one launcher (`*_go`) over a WProjArgs, and launch_wproj is a
+// switch over WProjPlan::kernel.
 #include <type_traits>
-
-#include <cstdlib>
 
 #include "common.hpp"
 #include "kernels.hpp"
@@ -49,7 +51,7 @@ template <> struct WCfg<256> { static constexpr int WR = 2, WC = 2, G = 8; };
 template <> struct WCfg<512> { static constexpr int WR = 1, WC = 4, G = 8; };
 
 constexpr int RT = 4;   // 16-row MFMA tiles per wave
-constexpr int KS = 32;  // k per step (one MFMA deep)
+constexpr int KS = kWprojKStep;  // k per step (one MFMA deep)
 
 __device__ __forceinline__ s16x4 tr_read(const bf16_t* p) {
     typedef s16x4 __attribute__((address_space(3))) * lds_ptr;
@@ -1043,13 +1045,99 @@ __global__ __launch_bounds__(512) void wproj3_kernel(const bf16_t* __restrict__ 
         }
 }
 
+// ---- host side: one product's arguments, the launch of a kernel on them and the common tail ---------
+struct WProjArgs {
+    const void* A;  // column-major (lda), m x n, bf16 or e4m3 as p.fp8 says
+    int64_t lda, m, n;
+    const bf16_t *Shi, *Slo;  // the skinny operand's panels (Slo == nullptr: single pass)
+    const WProjPlan& p;
+    float *slabs, *Out;
+    hipStream_t s;
+    hipEvent_t done;  // (optional) recorded after the MFMA kernel, before the slab reduction
+    int64_t rows_out() const { return p.nn ? m : n; }
+    int64_t K() const { return p.nn ? n : m; }
+    float* o() const { return p.splits == 1 ? Out : slabs; }  // where the MFMA kernel writes
+    int64_t stride() const { return rows_out() * p.LP; }      // one K split's slab
+    int grid() const { return p.blocks * p.splits; }
+};
+
+// One launch of a 512-thread LDS-DMA kernel on `grid` workgroups, reading the S panels at Shi / Slo and
+// writing at o (a 256-column half starts inside the panels); x: the arguments after nrowblk
+template <typename AT, typename... X>
+void wproj_launch_at(void (*kern)(const AT*, int64_t, int64_t, int64_t, int64_t, const bf16_t*, const bf16_t*, float*,
+                                  int64_t, int64_t, int, X...),
+                     const WProjArgs& a, size_t lds, int grid, const bf16_t* Shi, const bf16_t* Slo, float* o, X... x) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, a.s, static_cast<const AT*>(a.A), a.lda, a.rows_out(), a.K(),
+                       a.m, Shi, Slo, o, a.stride(), a.p.chunk, a.p.blocks, x...);
+}
+// ... on the whole panels
+template <typename KERN, typename... X>
+void wproj_launch(KERN kern, const WProjArgs& a, size_t lds, X... x) {
+    wproj_launch_at(kern, a, lds, a.grid(), a.Shi, a.Slo, a.o(), x...);
+}
+
+// After the MFMA kernel(s): the launch error, the `done` event, and the sum of the K-split slabs
+hipError_t wproj_finish(const WProjArgs& a) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && a.done) e = hipEventRecord(a.done, a.s);
+    if (e != hipSuccess || a.p.splits == 1) return e;
+    return launch_sum_slabs<float>(a.slabs, a.stride(), a.p.splits, a.stride(), a.Out, a.s);
+}
+
+// A 256-column kernel on panels of LP = 256 or 512 columns (S and output pitch LP): at LP = 512 the
+// two halves in one merged launch (p.merge: twin blocks adjacent, A read once and the twin from L2)
+// or one launch per 256-column half (S columns 256 hf .., into output columns 256 hf ..); then the tail.
+// s_elem: bytes per element of the S panel (an e4m3 panel: 1).
+template <typename KERN>
+hipError_t wproj_halves_go(KERN kern, const WProjArgs& a, size_t lds, int s_elem = 2) {
+    const WProjPlan& p = a.p;
+    const int halves = p.LP / 256;
+    if (halves == 2 && p.merge) {
+        wproj_launch_at(kern, a, lds, 2 * a.grid(), a.Shi, a.Slo, a.o(), p.LP, p.LP, 2);
+    } else {
+        for (int hf = 0; hf < halves; ++hf) {
+            const bf16_t* sh = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(a.Shi) + 256 * hf * s_elem);
+            wproj_launch_at(kern, a, lds, a.grid(), sh, a.Slo ? a.Slo + 256 * hf : nullptr, a.o() + 256 * hf, p.LP,
+                            p.LP, 1);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;  // (do not start the second half after a failed first)
+        }
+    }
+    return wproj_finish(a);
+}
+
+// Runtime values as template arguments.  with_bools(f, b...) is f(std::bool_constant<b>{}...);
+// with_int<Vs...>(v, f) is f(std::integral_constant<int, v>{}) for v among Vs, else hipErrorInvalidValue.
+template <bool... Bs, typename F>
+hipError_t with_bools(F&& f) {
+    return f(std::bool_constant<Bs>{}...);
+}
+template <bool... Bs, typename F, typename... R>
+hipError_t with_bools(F&& f, bool b, R... r) {
+    return b ? with_bools<Bs..., true>(f, r...) : with_bools<Bs..., false>(f, r...);
+}
+template <int... Vs, typename F>
+hipError_t with_int(int v, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs && ((e = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return e;
+}
+
+// The kernel's knob set KN as a template argument of `go`; SWEEP (RSVD_LAB builds): the lab's knob
+// sweep replaces it by p.kn in 0..3
+template <int KN, bool SWEEP, typename F>
+void wproj_with_knobs(const WProjPlan& p, F&& go) {
+#ifdef RSVD_LAB
+    if constexpr (SWEEP) {
+        if (with_int<0, 1, 2, 3>(p.kn, [&](auto kn) { return go(kn), hipSuccess; }) == hipSuccess) return;
+    }
+#endif
+    go(std::integral_constant<int, KN>{});
+}
+
 template <bool NN, int LP, bool SPLIT, int SD, int ABL = 0>
-hipError_t wproj3_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
-                     const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
+hipError_t wproj3_go(const WProjArgs& a) {
     typedef W3Shape<LP, NN, SPLIT, SD> SH;
-    const int64_t rows_out = NN ? m : n, K = NN ? n : m;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * LP;
     // as v2 (profiles/r02_wide_lab_knobs.txt), plus the interleaved DMA (bit 2, round 6) for the LP = 256 NN
     // (C4 -0.23 ms on one box, bit-identical; the LP = 128 NN measured 4.99 -> 5.01 ms at C3 with it)
     constexpr int KN = NN ? ((LP == 256 && ABL == 0) ? 7 : 3) : 0;
@@ -1058,38 +1146,14 @@ hipError_t wproj3_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf1
 #else
     constexpr bool ar_ok = false;  // (the lab-only variants are built into tools/wide_lab alone)
 #endif
-    auto go = [&](auto knc) {
+    wproj_with_knobs<KN, LP == 256 && ABL == 0 && SD == 1>(a.p, [&](auto knc) {
         if constexpr (ar_ok) {
-            if (p.abl & 16) {  // abl 16 (lab only): register-staged A
-                hipLaunchKernelGGL((wproj3_kernel<NN, LP, SPLIT, decltype(knc)::value, SD, 0, true>),
-                                   dim3(p.blocks * p.splits), dim3(512), SH::LDS, s, reinterpret_cast<const bf16_t*>(A),
-                                   lda, rows_out, K, m, Shi, Slo, o, stride, p.chunk, p.blocks);
-                return;
-            }
+            if (a.p.abl & 16)  // abl 16 (lab only): register-staged A
+                return wproj_launch(wproj3_kernel<NN, LP, SPLIT, decltype(knc)::value, SD, 0, true>, a, SH::LDS);
         }
-        hipLaunchKernelGGL((wproj3_kernel<NN, LP, SPLIT, decltype(knc)::value, SD, ABL>), dim3(p.blocks * p.splits),
-                           dim3(512), SH::LDS, s, reinterpret_cast<const bf16_t*>(A), lda, rows_out, K, m, Shi, Slo, o,
-                           stride, p.chunk, p.blocks);
-    };
-#ifdef RSVD_LAB
-    if constexpr (LP == 256 && ABL == 0 && SD == 1) {  // lab knob sweep (p.kn >= 0); the engine uses KN
-        switch (p.kn < 0 ? KN : p.kn) {
-            case 0: go(std::integral_constant<int, 0>{}); break;
-            case 1: go(std::integral_constant<int, 1>{}); break;
-            case 2: go(std::integral_constant<int, 2>{}); break;
-            case 3: go(std::integral_constant<int, 3>{}); break;
-            default: go(std::integral_constant<int, KN>{}); break;
-        }
-    } else {
-        go(std::integral_constant<int, KN>{});
-    }
-#else
-    go(std::integral_constant<int, KN>{});
-#endif
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+        wproj_launch(wproj3_kernel<NN, LP, SPLIT, decltype(knc)::value, SD, ABL>, a, SH::LDS);
+    });
+    return wproj_finish(a);
 }
 
 // v3 TN at LP = 256 with two k-steps per A slot: the A image of a slot is [WI j][64 i] (128-B
@@ -1668,103 +1732,34 @@ constexpr size_t nn8_lds() {
 
 // e4m3 NN through wproj3nn8_kernel: LP = 512 as two 256-column halves (merged: one launch)
 template <bool SPLIT>
-hipError_t wproj3nn8_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
-                        const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
+hipError_t wproj3nn8_go(const WProjArgs& a) {
     constexpr size_t lds = nn8_lds<SPLIT>();
     static_assert(lds <= 163840, "NN8 LDS");
-    const int64_t rows_out = m, K = n;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * 512;
-    if (p.merge) {
-        hipLaunchKernelGGL((wproj3nn8_kernel<SPLIT, true>), dim3(2 * p.blocks * p.splits), dim3(512), lds, s,
-                           reinterpret_cast<const uint8_t*>(A), lda, rows_out, K, m, Shi, Slo, o, stride, p.chunk,
-                           p.blocks, 512, 512, 2);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    } else {
-        for (int hf = 0; hf < 2; ++hf) {
-            hipLaunchKernelGGL((wproj3nn8_kernel<SPLIT, true>), dim3(p.blocks * p.splits), dim3(512), lds, s,
-                               reinterpret_cast<const uint8_t*>(A), lda, rows_out, K, m, Shi + 256 * hf,
-                               Slo ? Slo + 256 * hf : nullptr, o + 256 * hf, stride, p.chunk, p.blocks, 512, 512, 1);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    }
-    hipError_t e = hipSuccess;
-    if (done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+    return wproj_halves_go(wproj3nn8_kernel<SPLIT, true>, a, lds);
 }
 
 // e4m3 TN through wproj3tn4_kernel: LP = 256 in one dispatch, LP = 512 as two 256-column halves
-// (S columns 256 hf .., pitch 512, into output columns 256 hf ..).
 template <bool SPLIT>
-hipError_t wproj3tn4_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo, int LP,
-                        const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
+hipError_t wproj3tn4_go(const WProjArgs& a) {
     typedef W3Shape<256, false, SPLIT, 1> SH;
     constexpr size_t lds = 2 * (size_t)SH::WI * 128 + 2 * (size_t)SH::SSLOT;
     static_assert(lds <= 163840, "TN4 LDS");
-    const int64_t rows_out = n, K = m;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * LP;
-    if (LP == 512 && p.merge) {  // both halves in one launch (A read once, the twin from L2)
-        hipLaunchKernelGGL((wproj3tn4_kernel<SPLIT>), dim3(2 * p.blocks * p.splits), dim3(512), lds, s,
-                           reinterpret_cast<const uint8_t*>(A), lda, rows_out, K, m, Shi, Slo, o, stride, p.chunk,
-                           p.blocks, LP, LP, 2);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    } else {
-        for (int hf = 0; hf < LP / 256; ++hf) {
-            hipLaunchKernelGGL((wproj3tn4_kernel<SPLIT>), dim3(p.blocks * p.splits), dim3(512), lds, s,
-                               reinterpret_cast<const uint8_t*>(A), lda, rows_out, K, m, Shi + 256 * hf,
-                               Slo ? Slo + 256 * hf : nullptr, o + 256 * hf, stride, p.chunk, p.blocks, LP, LP, 1);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    }
-    hipError_t e = hipSuccess;
-    if (done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+    return wproj_halves_go(wproj3tn4_kernel<SPLIT>, a, lds);
 }
 
 template <bool SPLIT>
-hipError_t wproj3tn2_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
-                        const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
+hipError_t wproj3tn2_go(const WProjArgs& a) {
     typedef W3Shape<256, false, SPLIT, 1> SH;
     constexpr size_t lds = 2 * (size_t)SH::WI * 128 + 2 * (size_t)SH::SSLOT;
     static_assert(lds <= 163840, "TN2 LDS");
-    const int64_t rows_out = n, K = m;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * 256;
-    auto go = [&](auto knc) {  // LDS-DMA A; register-staged A only for the lab (abl 16)
+    // KN 4: interleaved DMA (KN bit 2, round 6)
+    wproj_with_knobs<4, true>(a.p, [&](auto knc) {  // LDS-DMA A; register-staged A only for the lab (abl 16)
 #ifdef RSVD_LAB
-        if (p.abl & 16) {
-            hipLaunchKernelGGL((wproj3tn2_kernel<SPLIT, decltype(knc)::value, true>), dim3(p.blocks * p.splits),
-                               dim3(512), lds, s, reinterpret_cast<const bf16_t*>(A), lda, rows_out, K, m, Shi, Slo, o,
-                               stride, p.chunk, p.blocks);
-            return;
-        }
+        if (a.p.abl & 16) return wproj_launch(wproj3tn2_kernel<SPLIT, decltype(knc)::value, true>, a, lds);
 #endif
-        hipLaunchKernelGGL((wproj3tn2_kernel<SPLIT, decltype(knc)::value, false>), dim3(p.blocks * p.splits),
-                           dim3(512), lds, s, reinterpret_cast<const bf16_t*>(A), lda, rows_out, K, m, Shi, Slo, o,
-                           stride, p.chunk, p.blocks);
-    };
-#ifdef RSVD_LAB
-    switch (p.kn < 0 ? 4 : p.kn) {  // KN 4 (interleaved DMA) in the engine; the others for the lab knob sweep
-        case 0: go(std::integral_constant<int, 0>{}); break;
-        case 1: go(std::integral_constant<int, 1>{}); break;
-        case 2: go(std::integral_constant<int, 2>{}); break;
-        case 3: go(std::integral_constant<int, 3>{}); break;
-        default: go(std::integral_constant<int, 4>{}); break;
-    }
-#else
-    go(std::integral_constant<int, 4>{});  // interleaved DMA (KN bit 2, round 6)
-#endif
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+        wproj_launch(wproj3tn2_kernel<SPLIT, decltype(knc)::value, false>, a, lds);
+    });
+    return wproj_finish(a);
 }
 
 // bf16 TN at LP = 128 with separate A and S rings (C3: Z = A^T Q, 2^20 x 1024 A, K split 64 ways).
@@ -1942,298 +1937,139 @@ __global__ __launch_bounds__(512) void wproj3tn128_kernel(const bf16_t* __restri
         }
 }
 
-// ring depths (A slots, S slots): 4 / 2 in the engine; 3 / 3 in the lab only (p.tn3 = 2, RSVD_LAB builds)
+// ring depths (A slots, S slots): 4 / 2 in the engine; 3 / 3 in the lab only (p.rings33, RSVD_LAB builds)
 template <bool SPLIT>
-hipError_t wproj3tn128_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
-                          const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
+hipError_t wproj3tn128_go(const WProjArgs& a) {
     constexpr int NS = SPLIT ? 2 : 1;
-    const int64_t rows_out = n, K = m;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * 128;
 #ifdef RSVD_LAB
-    if (p.tn3 == 2)
-        hipLaunchKernelGGL((wproj3tn128_kernel<SPLIT, 3, 3>), dim3(p.blocks * p.splits), dim3(512),
-                           (Tn128Shape<3, 3>::lds(NS)), s, reinterpret_cast<const bf16_t*>(A), lda, rows_out, K, m, Shi,
-                           Slo, o, stride, p.chunk, p.blocks);
+    if (a.p.rings33)
+        wproj_launch(wproj3tn128_kernel<SPLIT, 3, 3>, a, Tn128Shape<3, 3>::lds(NS));
     else
 #endif
-        hipLaunchKernelGGL((wproj3tn128_kernel<SPLIT, 4, 2>), dim3(p.blocks * p.splits), dim3(512),
-                           (Tn128Shape<4, 2>::lds(NS)), s, reinterpret_cast<const bf16_t*>(A), lda, rows_out, K, m, Shi,
-                           Slo, o, stride, p.chunk, p.blocks);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+        wproj_launch(wproj3tn128_kernel<SPLIT, 4, 2>, a, Tn128Shape<4, 2>::lds(NS));
+    return wproj_finish(a);
 }
 
+// NN streams A in whole columns: non-temporal A (and the static priority) measured -9..-11 % on
+// the C3 / C4 / C5 NN launches; TN's short column runs need the L2 to keep the second half of
+// each line for the next k-step (non-temporal: +4..13 %), so TN keeps the default policy
+// (profiles/r02_wide_lab_knobs.txt).
+template <bool NN>
+constexpr int kW2Knobs = NN ? 3 : 0;
 
 template <bool FP8, bool NN, int LP, bool SPLIT, bool DS = false, bool S8 = false, bool SC = false>
-hipError_t wproj2_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
-                     const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
+hipError_t wproj2_go(const WProjArgs& a) {
     typedef W2Shape<LP, SPLIT, FP8, DS, S8, SC> SH;
-    const int64_t rows_out = NN ? m : n, K = NN ? n : m;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * LP;
-    // NN streams A in whole columns: non-temporal A (and the static priority) measured -9..-11 % on
-    // the C3 / C4 / C5 NN launches; TN's short column runs need the L2 to keep the second half of
-    // each line for the next k-step (non-temporal: +4..13 %), so TN keeps the default policy
-    // (profiles/r02_wide_lab_knobs.txt).
-    constexpr int KN = NN ? 3 : 0;
-    hipLaunchKernelGGL((wproj2_kernel<FP8, NN, LP, SPLIT, DS, KN, S8, SC>), dim3(p.blocks * p.splits), dim3(512), SH::LDS,
-                       s, A, lda, rows_out, K, m, Shi, Slo, o, stride, p.chunk, p.blocks, LP, LP, 1);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+    wproj_launch(wproj2_kernel<FP8, NN, LP, SPLIT, DS, kW2Knobs<NN>, S8, SC>, a, SH::LDS, LP, LP, 1);
+    return wproj_finish(a);
 }
 
-// LP = 512 as two LP = 256 column halves (WProjPlan::half).  At LP = 512 the v2 tile is 128 output
+// LP = 512 as two LP = 256 column halves (WProjKernel::W2Half).  At LP = 512 the v2 tile is 128 output
 // rows x 512 columns, so every workgroup re-reads 16x (NN) / 16x (TN) more S bytes from L2 than A
 // bytes (C5 TN: 16 GB of S per launch against 1.07 GB of A, and the L2 pressure evicted A's line
 // halves before the next k-step used them: 4x A traffic from HBM).  Each half runs the LP = 256
 // tile (256 rows x 256 columns: S 2x A per k-step) on its 256 columns of S (pitch 512) into its
 // 256 columns of the output / slabs (pitch 512).  Same per-element arithmetic: bit-identical.
-template <bool FP8, bool NN, bool SPLIT, bool S8 = false, bool SC = false>
-hipError_t wproj2_half_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
-                          const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
-    typedef W2Shape<256, SPLIT, FP8, false, S8, SC> SH;
-    const int64_t rows_out = NN ? m : n, K = NN ? n : m;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * 512;
-    constexpr int KN = NN ? 3 : 0;
-    if (p.merge) {  // both halves in one launch: neighbouring blocks share the A tile through the L2
-        hipLaunchKernelGGL((wproj2_kernel<FP8, NN, 256, SPLIT, false, KN, S8, SC>), dim3(2 * p.blocks * p.splits),
-                           dim3(512), SH::LDS, s, A, lda, rows_out, K, m, Shi, Slo, o, stride, p.chunk, p.blocks, 512,
-                           512, 2);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    } else {
-        for (int hf = 0; hf < 2; ++hf) {
-            // S column offset: 256 bf16 elements, or 256 bytes of an e4m3 panel (S8)
-            const bf16_t* sh = S8 ? reinterpret_cast<const bf16_t*>(reinterpret_cast<const uint8_t*>(Shi) + 256 * hf)
-                                  : Shi + 256 * hf;
-            const bf16_t* sl = Slo ? Slo + 256 * hf : nullptr;
-            hipLaunchKernelGGL((wproj2_kernel<FP8, NN, 256, SPLIT, false, KN, S8, SC>), dim3(p.blocks * p.splits),
-                               dim3(512), SH::LDS, s, A, lda, rows_out, K, m, sh, sl, o + 256 * hf, stride, p.chunk,
-                               p.blocks, 512, 512, 1);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    }
-    hipError_t e = hipSuccess;
-    if (done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+// (the e4m3 NN only: every e4m3 TN takes wproj3tn4)
+template <bool SPLIT, bool S8 = false, bool SC = false>
+hipError_t wproj2_half_go(const WProjArgs& a) {
+    typedef W2Shape<256, SPLIT, true, false, S8, SC> SH;
+    // S column offset of a half: 256 bf16 elements, or 256 bytes of an e4m3 panel (S8)
+    return wproj_halves_go(wproj2_kernel<true, true, 256, SPLIT, false, kW2Knobs<true>, S8, SC>, a, SH::LDS, S8 ? 1 : 2);
 }
 
 template <bool FP8, bool NN, int LP, bool SPLIT>
-hipError_t wproj_go(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
-                    const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
-    const int64_t rows_out = NN ? m : n, K = NN ? n : m;
-    float* o = p.splits == 1 ? Out : slabs;
-    const int64_t stride = rows_out * LP;
+hipError_t wproj_go(const WProjArgs& a) {
     const int esz = FP8 ? 1 : 2;
-    const int vec_ok = ((lda * esz) % 16 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
-    hipLaunchKernelGGL((wproj_kernel<FP8, NN, LP, SPLIT>), dim3(p.blocks * p.splits), dim3(256),
-                       (wproj_lds<FP8, NN, LP, SPLIT>()), s, A, lda, rows_out, K, Shi, Slo, o, stride, p.chunk,
-                       p.blocks, vec_ok);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && done) e = hipEventRecord(done, s);
-    if (e != hipSuccess || p.splits == 1) return e;
-    return launch_sum_slabs<float>(slabs, stride, p.splits, stride, Out, s);
+    const int vec_ok = ((a.lda * esz) % 16 == 0) && ((reinterpret_cast<uintptr_t>(a.A) & 15) == 0);
+    hipLaunchKernelGGL((wproj_kernel<FP8, NN, LP, SPLIT>), dim3(a.grid()), dim3(256), (wproj_lds<FP8, NN, LP, SPLIT>()),
+                       a.s, a.A, a.lda, a.rows_out(), a.K(), a.Shi, a.Slo, a.o(), a.stride(), a.p.chunk, a.p.blocks,
+                       vec_ok);
+    return wproj_finish(a);
 }
 
+// The launcher of the plan's kernel at sketch width LP.  Every case instantiates exactly the products
+// its kernel is built for (wproj_plan_valid, checked by launch_wproj before it comes here).
 template <int LP>
-hipError_t wproj_lp(int nn, int fp8, const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi,
-                    const bf16_t* Slo, const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t d) {
-    const bool split = Slo != nullptr;
-    if constexpr (LP == 128) {
-        // the v3 NN at LP = 128 (WI = 512 rows, A 3 / S 2 slots) for the hi / lo products: C3 5.40 ->
-        // 5.35 ms (gpurun_out r6d, bit-identical); the single-pass sketch measured 468 -> 473 us on it
-        // and keeps v2
-        if (p.v2 && nn && !fp8 && p.nn3 && split)
-            return wproj3_go<true, 128, true, 1>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-        if (p.v2 && p.ds && !nn && !fp8 && p.tn3)
-            return split ? wproj3tn128_go<true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)
-                         : wproj3tn128_go<false>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-        if (p.v2 && p.ds && !nn && !fp8)
-            return split ? wproj2_go<false, false, 128, true, true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)
-                         : wproj2_go<false, false, 128, false, true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-    }
-    if constexpr (LP == 256 || LP == 512) {
-        if (p.v2 && p.v3 && !fp8) {
-#define GO3(SD)                                                                                         \
-    {                                                                                                   \
-        if (nn) return split ? wproj3_go<true, LP, true, SD>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d) \
-                             : wproj3_go<true, LP, false, SD>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d); \
-        return split ? wproj3_go<false, LP, true, SD>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)        \
-                     : wproj3_go<false, LP, false, SD>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);      \
-    }
+hipError_t wproj_lp(const WProjArgs& a) {
+    typedef WProjKernel W;
+    const WProjPlan& p = a.p;
+    const bool split = a.Slo != nullptr;
+    const W k = wproj_kernel_for(p, split);
 #ifdef RSVD_LAB
-            if constexpr (LP == 256) {  // lab ablations of the C4 NN2 / TN2 kernels
-                if (p.abl && split) {
-#define AB(X) \
-    case X: return nn ? wproj3_go<true, 256, true, 1, X>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d) \
-                      : wproj3_go<false, 256, true, 1, X>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-                    switch (p.abl) { AB(1) AB(2) AB(3) AB(4) AB(5) AB(6) AB(7) default: break; }
-#undef AB
-                }
-            }
+    if constexpr (LP == 256) {  // lab ablations of the C4 NN2 / TN2 kernels (p.abl 1..7, hi / lo products)
+        if ((k == W::W3 || k == W::W3Tn2) && split && p.abl >= 1 && p.abl <= 7)
+            return with_int<1, 2, 3, 4, 5, 6, 7>(p.abl, [&](auto abl) {
+                return with_bools([&](auto nn) { return wproj3_go<nn(), 256, true, 1, decltype(abl)::value>(a); }, p.nn);
+            });
+    }
 #endif
-            if constexpr (LP == 256) {
-                // (round 6: the S panel two steps ahead instead of one -- sketch 1977 -> 2003 us at C4;
-                // profiles/r06_deadends.txt 22 -- so every v3 product keeps SD = 1)
-                if (!nn && p.tn2)
-                    return split ? wproj3tn2_go<true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)
-                                 : wproj3tn2_go<false>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-            }
-            GO3(1);
-#undef GO3
-        }
+    switch (k) {
+        case W::Fallback:
+            return with_bools([&](auto f8, auto nn, auto sp) { return wproj_go<f8(), nn(), LP, sp()>(a); }, p.fp8, p.nn,
+                              split);
+        case W::W2:
+            if constexpr (LP == 128)
+                return with_bools([&](auto f8, auto nn, auto sp) { return wproj2_go<f8(), nn(), 128, sp()>(a); }, p.fp8,
+                                  p.nn, split);
+            if constexpr (LP == 256)  // the e4m3 NN
+                return with_bools([&](auto sp) { return wproj2_go<true, true, 256, sp()>(a); }, split);
+            break;
+        case W::W2Ds:
+            if constexpr (LP == 128)
+                return with_bools([&](auto sp) { return wproj2_go<false, false, 128, sp(), true>(a); }, split);
+            break;
+        case W::W2Half:
+            if constexpr (LP == 512) return with_bools([&](auto sp) { return wproj2_half_go<sp()>(a); }, split);
+            break;
+        case W::W3:
+            if constexpr (LP == 128) return wproj3_go<true, 128, true, 1>(a);  // (NN hi / lo only: wproj_kernel_for)
+            // (round 6: the S panel two steps ahead instead of one -- sketch 1977 -> 2003 us at C4;
+            // profiles/r06_deadends.txt 22 -- so every v3 product keeps SD = 1)
+            if constexpr (LP == 256 || LP == 512)
+                return with_bools([&](auto nn, auto sp) { return wproj3_go<nn(), LP, sp(), 1>(a); }, p.nn, split);
+            break;
+        case W::W3Tn2:
+            if constexpr (LP == 256) return with_bools([&](auto sp) { return wproj3tn2_go<sp()>(a); }, split);
+            break;
+        case W::W3Tn128:
+            if constexpr (LP == 128) return with_bools([&](auto sp) { return wproj3tn128_go<sp()>(a); }, split);
+            break;
+        case W::W3Tn4:
+            if constexpr (LP == 256 || LP == 512)
+                return with_bools([&](auto sp) { return wproj3tn4_go<sp()>(a); }, split);
+            break;
+        case W::W3Nn8:
+            if constexpr (LP == 512) return with_bools([&](auto sp) { return wproj3nn8_go<sp()>(a); }, split);
+            break;
     }
-    if constexpr (LP == 256 || LP == 512) {
-        if (p.tn4 && fp8 && !nn)
-            return split ? wproj3tn4_go<true>(A, lda, m, n, Shi, Slo, LP, p, slabs, Out, s, d)
-                         : wproj3tn4_go<false>(A, lda, m, n, Shi, Slo, LP, p, slabs, Out, s, d);
-    }
-    if constexpr (LP == 512) {
-        if (p.v2 && p.half && fp8) {
-            if (nn && p.nn8)
-                return split ? wproj3nn8_go<true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)
-                             : wproj3nn8_go<false>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-            // (RSVD_NN8=0, the round-4 kernel; every v2 e4m3 TN takes wproj3tn4 above)
-            return split ? wproj2_half_go<true, true, true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)
-                         : wproj2_half_go<true, true, false>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-        }
-    }
-    if constexpr (LP >= 128) {
-        if (p.v2) {
-#define GO2(F)                                                                                   \
-    {                                                                                            \
-        if (nn) return split ? wproj2_go<F, true, LP, true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d) \
-                             : wproj2_go<F, true, LP, false>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d); \
-        return split ? wproj2_go<F, false, LP, true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)        \
-                     : wproj2_go<F, false, LP, false>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);      \
-    }
-            if (fp8) {  // (e4m3 at LP 256 / 512: the TN is wproj3tn4's, LP 512 runs as halves above)
-                if constexpr (LP == 128) GO2(true);
-                if constexpr (LP == 256) {
-                    if (nn) return split ? wproj2_go<true, true, LP, true>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)
-                                         : wproj2_go<true, true, LP, false>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d);
-                }
-                return hipErrorInvalidValue;
-            }
-            if constexpr (LP == 128) GO2(false);  // (bf16 at LP 256 / 512: the v3 kernels above)
-            return hipErrorInvalidValue;
-#undef GO2
-        }
-    }
-#define GO(F, N, SP) return wproj_go<F, N, LP, SP>(A, lda, m, n, Shi, Slo, p, slabs, Out, s, d)
-    if (fp8) {
-        if (nn) { if (split) GO(true, true, true); GO(true, true, false); }
-        if (split) GO(true, false, true);
-        GO(true, false, false);
-    }
-    if (nn) { if (split) GO(false, true, true); GO(false, true, false); }
-    if (split) GO(false, false, true);
-    GO(false, false, false);
-#undef GO
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-bool wproj_supported_lp(int LP) {
-    return LP == 16 || LP == 32 || LP == 64 || LP == 128 || LP == 256 || LP == 512;
-}
-
-int wproj_rows_per_block(int LP) { return LP <= 128 ? 256 : (LP == 256 ? 128 : 64); }
-
-static int tn128_mode() {  // RSVD_TN128: 0 the v2 double-step LP = 128 TN, 1 rings 4 / 2 (default)
-    static const int env = [] {
-        const char* v = std::getenv("RSVD_TN128");
-        const int x = v ? std::atoi(v) : 1;
-        return x == 0 ? 0 : 1;
-    }();
-    return env;
-}
-
-static bool nn8_enabled() {  // RSVD_NN8=0 in the environment: the v2 e4m3 NN (A/B)
-    static const int env = [] {
-        const char* v = std::getenv("RSVD_NN8");
-        return v ? std::atoi(v) : 1;
-    }();
-    return env != 0;
-}
-
-static bool nn3_128_enabled() {  // RSVD_NN3_128=0 in the environment: the v2 bf16 NN at LP = 128 (A/B)
-    static const int env = [] {
-        const char* v = std::getenv("RSVD_NN3_128");
-        return v ? std::atoi(v) : 1;
-    }();
-    return env != 0;
-}
-
-WProjPlan plan_wproj(int64_t rows_out, int64_t K, int LP, bool v2, bool nn, bool fp8) {
-    WProjPlan p;
-    p.v2 = v2 && LP >= 128;
-    p.v3 = p.v2 && !fp8 && (LP == 256 || LP == 512);
-    p.tn2 = p.v3 && !nn && LP == 256;  // two k-steps per A slot: K chunks of whole 64-row pairs
-    p.ds = p.v2 && LP == 128 && !nn && !fp8 && K % 64 == 0;  // double-step TN stages (whole 64-row K chunks)
-    p.tn3 = p.ds ? tn128_mode() : 0;
-    p.nn3 = p.v2 && LP == 128 && nn && !fp8 && nn3_128_enabled();
-    p.half = p.v2 && fp8 && LP == 512;  // two LP = 256 column halves (wproj2_half_go)
-    p.nn8 = p.half && nn && nn8_enabled();  // ... the e4m3 NN on wproj3nn8_kernel
-    // e4m3 TN: four k-steps per A slot (wproj3tn4_kernel; K chunks of whole 128-row slots)
-    p.tn4 = p.v2 && fp8 && !nn && (LP == 256 || LP == 512);
-    const int WI = p.v2 ? (LP == 128 ? (p.ds ? 256 : 512) : ((LP == 256 || p.half) ? 256 : 128))
-                        : wproj_rows_per_block(LP);
-    p.blocks = (int)((rows_out + WI - 1) / WI);
-    // LP = 512 e4m3 products as two 256-column halves in one launch (twin workgroups adjacent)
-    p.merge = p.half || (p.tn4 && LP == 512);
-    // one workgroup per CU (LDS ring / registers); merged halves: two workgroups per (row block, split)
-    const int target = p.merge ? 128 : ((p.v2 || LP >= 512) ? 256 : 512);
-    int64_t splits = (target + p.blocks - 1) / p.blocks;
-    const int64_t max_by_work = K / (KS * 8);
-    if (splits > max_by_work) splits = max_by_work;
-    if (splits > 128) splits = 128;
-    if (splits < 1) splits = 1;
-    int64_t chunk = (K + splits - 1) / splits;
-    const int kq = p.tn4 ? 4 * KS : ((p.ds || p.tn2) ? 2 * KS : KS);
-    chunk = (chunk + kq - 1) / kq * kq;
-    p.chunk = chunk;
-    p.splits = (int)((K + chunk - 1) / chunk);
-    return p;
-}
-
-bool wproj_s8_supported(const WProjPlan& p, int LP) { return p.v2 && (LP == 256 || LP == 512); }
-
-hipError_t launch_wproj_s8(const void* A, int64_t lda, int64_t m, int64_t n, const fp8_t* S8, int LP, const WProjPlan& p,
+hipError_t launch_wproj_s8(const void* A, int64_t lda, int64_t m, int64_t n, const fp8_t* S8, const WProjPlan& p,
                            float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
-    if (!wproj_s8_supported(p, LP)) return hipErrorInvalidValue;
-    const bf16_t* S = reinterpret_cast<const bf16_t*>(S8);
-    // the block-scaled K = 128 form when every stage is whole (else the K = 32 form)
-    const bool sc = n % 128 == 0 && p.chunk % 128 == 0;
-    if (sc) {
-        if (LP == 256) return wproj2_go<true, true, 256, false, false, true, true>(A, lda, m, n, S, nullptr, p, slabs, Out, s, done);
-        if (p.half) return wproj2_half_go<true, true, false, true, true>(A, lda, m, n, S, nullptr, p, slabs, Out, s, done);
-    }
-    if (LP == 256) return wproj2_go<true, true, 256, false, false, true>(A, lda, m, n, S, nullptr, p, slabs, Out, s, done);
-    if (p.half) return wproj2_half_go<true, true, false, true>(A, lda, m, n, S, nullptr, p, slabs, Out, s, done);
-    return wproj2_go<true, true, 512, false, false, true>(A, lda, m, n, S, nullptr, p, slabs, Out, s, done);
+    if (!wproj_plan_valid(p) || !wproj_s8_supported(p)) return hipErrorInvalidValue;
+    const WProjArgs a{A, lda, m, n, reinterpret_cast<const bf16_t*>(S8), nullptr, p, slabs, Out, s, done};
+    return with_bools(
+        [&](auto sc) {
+            switch (p.kernel) {
+                case WProjKernel::W2: return wproj2_go<true, true, 256, false, false, true, sc()>(a);  // LP = 256
+                case WProjKernel::W2Half:  // LP = 512: the sketch runs as wproj2 halves next to either NN kernel
+                case WProjKernel::W3Nn8: return wproj2_half_go<false, true, sc()>(a);
+                default: return hipErrorInvalidValue;
+            }
+        },
+        p.s8_scaled);
 }
 
-hipError_t launch_wproj(int nn, int a_fp8, const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi,
-                        const bf16_t* Slo, int LP, const WProjPlan& p, float* slabs, float* Out, hipStream_t s,
-                        hipEvent_t done) {
-    switch (LP) {
-        case 16: return wproj_lp<16>(nn, a_fp8, A, lda, m, n, Shi, Slo, p, slabs, Out, s, done);
-        case 32: return wproj_lp<32>(nn, a_fp8, A, lda, m, n, Shi, Slo, p, slabs, Out, s, done);
-        case 64: return wproj_lp<64>(nn, a_fp8, A, lda, m, n, Shi, Slo, p, slabs, Out, s, done);
-        case 128: return wproj_lp<128>(nn, a_fp8, A, lda, m, n, Shi, Slo, p, slabs, Out, s, done);
-        case 256: return wproj_lp<256>(nn, a_fp8, A, lda, m, n, Shi, Slo, p, slabs, Out, s, done);
-        case 512: return wproj_lp<512>(nn, a_fp8, A, lda, m, n, Shi, Slo, p, slabs, Out, s, done);
-        default: return hipErrorInvalidValue;
-    }
+hipError_t launch_wproj(const void* A, int64_t lda, int64_t m, int64_t n, const bf16_t* Shi, const bf16_t* Slo,
+                        const WProjPlan& p, float* slabs, float* Out, hipStream_t s, hipEvent_t done) {
+    // a plan whose kernel is not built for its LP / nn / fp8 stops here, whatever the cases below would do
+    if (!wproj_plan_valid(p)) return hipErrorInvalidValue;
+    const WProjArgs a{A, lda, m, n, Shi, Slo, p, slabs, Out, s, done};
+    return with_int<16, 32, 64, 128, 256, 512>(p.LP, [&](auto lp) { return wproj_lp<decltype(lp)::value>(a); });
 }
 
 }  // namespace rsvd

@@ -3,11 +3,13 @@ mirror of the projection planners (a plain helper module, shared by test_ragged_
 CPU and test_gpu_ragged.py on the GPU).
 
 Each row is the smallest shape found at which the named kernel branch is still taken.  The branch
-and the K-split counts written next to a row were derived from plan_wproj (csrc/wide_proj.hip, KS =
-32), WideLayout's v2 / s8 conditions (csrc/wide.cpp), launch_wproj_s8's block-scaled test and
-make_plan (csrc/proj.hip); `plan()` below is that derivation as code and test_ragged_inputs.py
-checks the table against it.  The mirror documents the table -- the GPU test still asserts the
-engine's own rsvd_get_info splits, so a planner change that moves a case off its branch fails there.
+and the K-split counts written next to a row were derived from plan_wproj (csrc/wide_plan.cpp, k
+step 32) with its block-scaled test of the e4m3 sketch, WideLayout's v2 / s8 conditions
+(csrc/wide.cpp) and make_plan (csrc/proj.hip); `plan()` below is that derivation as code and
+test_ragged_inputs.py checks the table against it.  The mirror keeps its own flag names: it is the
+independent restatement, and test_wproj_plan.py compares it with the real planner on the CPU.  The
+GPU test still asserts the engine's own rsvd_get_info splits, so a planner change that moves a case
+off its branch fails there too.
 """
 from collections import namedtuple
 from functools import lru_cache
@@ -36,7 +38,7 @@ def lowp_lp(l):
 
 
 def plan_wproj(rows_out, K, LP, v2=False, nn=True, fp8=False):
-    """plan_wproj (csrc/wide_proj.hip) with the diagnostic environment switches at their defaults."""
+    """plan_wproj (csrc/wide_plan.cpp) with the diagnostic environment switches at their defaults."""
     p = {}
     p["v2"] = v2 and LP >= 128
     p["v3"] = p["v2"] and not fp8 and LP in (256, 512)
@@ -70,7 +72,7 @@ def make_plan(K, blocks, kstep_wg):
 
 
 def _nn_kernel(p, LP, fp8, split):
-    """wproj_lp's dispatch (csrc/wide_proj.hip) for Y = A X; split: the hi / lo operand pair."""
+    """The kernel plan_wproj (csrc/wide_plan.cpp) names for Y = A X; split: the hi / lo operand pair."""
     if not p["v2"]:
         return "wproj"
     if LP == 128:

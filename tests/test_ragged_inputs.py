@@ -54,7 +54,7 @@ def test_branch_follows_from_planner_mirror(cid):
 
 
 def test_mirror_hand_derived_plans():
-    """Plans worked out by hand from csrc/wide_proj.hip and csrc/proj.hip, independent of the table."""
+    """Plans worked out by hand from csrc/wide_plan.cpp and csrc/proj.hip, independent of the table."""
     # e4m3 1024 x 1152, LP 256, v2: NN 4 row blocks of 256, target 256 -> 64 splits, capped by
     # K / 256 = 4; chunk 288 is no multiple of 128, so the sketch takes the K = 32 form
     p = rc.plan_wproj(1024, 1152, 256, True, True, True)

@@ -424,6 +424,15 @@ __global__ void fill_random_kernel(uint16_t* p, size_t n16, int fp8) {
     }
 }
 
+// the plan runs the v3 kernels of bf16 A at LP 256 / 512 (wproj3_kernel, wproj3tn2_kernel)
+static bool plan_is_v3(const WProjPlan& p) {
+    return (p.kernel == WProjKernel::W3 && p.LP >= 256) || p.kernel == WProjKernel::W3Tn2;
+}
+// the v3 TN at LP = 256 with single-step A slots (wproj3_kernel) instead of wproj3tn2_kernel
+static void plan_tn2_off(WProjPlan& p) {
+    if (p.kernel == WProjKernel::W3Tn2) p.kernel = WProjKernel::W3;
+}
+
 static void bench_proj(bool c4only = false) {
     struct Case { int64_t m, n; int LP; int fp8; };
     for (Case c : {Case{1 << 20, 1024, 128, 0}, Case{65536, 65536, 256, 0}, Case{131072, 8192, 512, 1}}) {
@@ -440,15 +449,16 @@ static void bench_proj(bool c4only = false) {
         CK(hipMalloc(&Out, (size_t)mx * c.LP * 4));
         for (int v2 = c4only ? 1 : 0; v2 < 4; ++v2) {
             WProjPlan pnn = plan_wproj(c.m, c.n, c.LP, v2 > 0, true, c.fp8), ptn = plan_wproj(c.n, c.m, c.LP, v2 > 0, false, c.fp8);
-            if (v2 == 1) pnn.v3 = ptn.v3 = false;
-            if (v2 >= 2 && !pnn.v3 && !ptn.v3) continue;
-            if (v2 == 3) ptn.tn2 = false;  // v3 TN with single-step A slots
+            // row "v2": the plans off the v3 kernels (LP = 128, e4m3); bf16 at LP 256 / 512 has no v2 kernel
+            const bool v3 = plan_is_v3(pnn) || plan_is_v3(ptn);
+            if (v2 == 1 ? v3 : (v2 >= 2 && !v3)) continue;
+            if (v2 == 3) plan_tn2_off(ptn);  // v3 TN with single-step A slots
             float* slabs;
             CK(hipMalloc(&slabs, (size_t)std::max<int64_t>(pnn.splits * c.m, ptn.splits * c.n) * c.LP * 4));
             const double bytes = (double)c.m * c.n * esz, fl = 2.0 * c.m * c.n * c.LP;
-            double t1 = time_us([&] { CK(launch_wproj(1, c.fp8, A, c.m, c.m, c.n, Sh, nullptr, c.LP, pnn, slabs, Out, S)); });
-            double t2 = time_us([&] { CK(launch_wproj(1, c.fp8, A, c.m, c.m, c.n, Sh, Sl, c.LP, pnn, slabs, Out, S)); });
-            double t3 = time_us([&] { CK(launch_wproj(0, c.fp8, A, c.m, c.m, c.n, Sh, Sl, c.LP, ptn, slabs, Out, S)); });
+            double t1 = time_us([&] { CK(launch_wproj(A, c.m, c.m, c.n, Sh, nullptr, pnn, slabs, Out, S)); });
+            double t2 = time_us([&] { CK(launch_wproj(A, c.m, c.m, c.n, Sh, Sl, pnn, slabs, Out, S)); });
+            double t3 = time_us([&] { CK(launch_wproj(A, c.m, c.m, c.n, Sh, Sl, ptn, slabs, Out, S)); });
             printf("proj%s m=%ld n=%ld LP=%d fp8=%d: NN1 %.1f us (%.0f GB/s) NN2 %.1f us (%.0f GB/s, %.0f TF) TN2 %.1f us"
                    " (%.0f GB/s, %.0f TF) splits nn=%d tn=%d\n",
                    v2 == 3 ? "v3(tn1)" : (v2 == 2 ? "v3" : (v2 ? "v2" : "v1")), (long)c.m, (long)c.n, c.LP, c.fp8, t1, bytes / t1 / 1e3, t2, bytes / t2 / 1e3,
@@ -476,10 +486,10 @@ static void bench_c5_stride() {
         WProjPlan pnn = plan_wproj(m, n, LP, true, true, true), ptn = plan_wproj(n, m, LP, true, false, true);
         float* slabs;
         CK(hipMalloc(&slabs, (size_t)std::max<int64_t>(pnn.splits * m, ptn.splits * n) * LP * 4));
-        double t2 = time_us([&] { CK(launch_wproj(1, 1, A, lda, m, n, Sh, Sl, LP, pnn, slabs, Out, S)); });
-        double t3 = time_us([&] { CK(launch_wproj(0, 1, A, lda, m, n, Sh, Sl, LP, ptn, slabs, Out, S)); });
-        printf("C5 e4m3 LP=512 lda=m+%ld: NN2 %.1f us  TN2 %.1f us (half=%d, splits nn=%d tn=%d)\n", (long)pad, t2, t3,
-               (int)ptn.half, pnn.splits, ptn.splits);
+        double t2 = time_us([&] { CK(launch_wproj(A, lda, m, n, Sh, Sl, pnn, slabs, Out, S)); });
+        double t3 = time_us([&] { CK(launch_wproj(A, lda, m, n, Sh, Sl, ptn, slabs, Out, S)); });
+        printf("C5 e4m3 LP=512 lda=m+%ld: NN2 %.1f us  TN2 %.1f us (%s / %s, splits nn=%d tn=%d)\n", (long)pad, t2, t3,
+               wproj_kernel_name(pnn.kernel), wproj_kernel_name(ptn.kernel), pnn.splits, ptn.splits);
         CK(hipFree(slabs)); CK(hipFree(A)); CK(hipFree(Sh)); CK(hipFree(Sl)); CK(hipFree(Out));
     }
 }
@@ -575,10 +585,10 @@ static void check_proj() {  // v2 (LDS-DMA) against v1 on random bf16 / e4m3 dat
             const int64_t ro = nn ? m : n, K = nn ? n : m;
             WProjPlan p1 = plan_wproj(ro, K, LP, false, nn, fp8), p2 = plan_wproj(ro, K, LP, true, nn, fp8);
             for (int m32 = 0; m32 < 2; ++m32) {
-            if (m32) p2.tn2 = false;
-            if (m32 && !p2.v3) continue;
-            CK(launch_wproj(nn, fp8, A, m, m, n, Sh, Sl, LP, p1, sl, O1, S));
-            CK(launch_wproj(nn, fp8, A, m, m, n, Sh, Sl, LP, p2, sl, O2, S));
+            if (m32 && !plan_is_v3(p2)) continue;
+            if (m32) plan_tn2_off(p2);
+            CK(launch_wproj(A, m, m, n, Sh, Sl, p1, sl, O1, S));
+            CK(launch_wproj(A, m, m, n, Sh, Sl, p2, sl, O2, S));
             CK(hipStreamSynchronize(S));
             std::vector<float> a(ro * LP), b(ro * LP);
             CK(hipMemcpy(a.data(), O1, a.size() * 4, hipMemcpyDeviceToHost));
@@ -588,8 +598,8 @@ static void check_proj() {  // v2 (LDS-DMA) against v1 on random bf16 / e4m3 dat
                 md = std::max(md, (double)fabs(a[i] - b[i]));
                 mx2 = std::max(mx2, (double)fabs(a[i]));
             }
-            printf("check fp8=%d LP=%d %s%s: max|v1-v2| = %.3e (max|v1| = %.3e) v2 splits=%d chunk=%ld\n",
-                   fp8, LP, nn ? "NN" : "TN", m32 ? " v3(tn1)" : (p2.v3 ? (p2.tn2 ? " v3tn2" : " v3") : ""), md, mx2, p2.splits, (long)p2.chunk);
+            printf("check fp8=%d LP=%d %s %s: max|v1-v2| = %.3e (max|v1| = %.3e) v2 splits=%d chunk=%ld\n",
+                   fp8, LP, nn ? "NN" : "TN", wproj_kernel_name(p2.kernel), md, mx2, p2.splits, (long)p2.chunk);
             }
         }
         CK(hipFree(A)); CK(hipFree(Sh)); CK(hipFree(Sl)); CK(hipFree(O1)); CK(hipFree(O2)); CK(hipFree(sl));
@@ -648,8 +658,8 @@ static void check_s8() {
             bad += !(back[i] == hS8[i] || (z1 && z2));
         }
         WProjPlan p = plan_wproj(m, n, LP, true, true, true);
-        CK(launch_wproj(1, 1, A, m, m, n, Sb, nullptr, LP, p, sl, O1, S));
-        CK(launch_wproj_s8(A, m, m, n, reinterpret_cast<const fp8_t*>(S8), LP, p, sl, O2, S));
+        CK(launch_wproj(A, m, m, n, Sb, nullptr, p, sl, O1, S));
+        CK(launch_wproj_s8(A, m, m, n, reinterpret_cast<const fp8_t*>(S8), p, sl, O2, S));
         CK(hipStreamSynchronize(S));
         std::vector<float> a(m * LP), b(m * LP);
         CK(hipMemcpy(a.data(), O1, a.size() * 4, hipMemcpyDeviceToHost));
@@ -660,8 +670,8 @@ static void check_s8() {
             mx = std::max(mx, (double)fabs(a[i]));
         }
         const double bytes = (double)m * n;
-        double t1 = time_us([&] { CK(launch_wproj(1, 1, A, m, m, n, Sb, nullptr, LP, p, sl, O1, S)); });
-        double t2 = time_us([&] { CK(launch_wproj_s8(A, m, m, n, reinterpret_cast<const fp8_t*>(S8), LP, p, sl, O2, S)); });
+        double t1 = time_us([&] { CK(launch_wproj(A, m, m, n, Sb, nullptr, p, sl, O1, S)); });
+        double t2 = time_us([&] { CK(launch_wproj_s8(A, m, m, n, reinterpret_cast<const fp8_t*>(S8), p, sl, O2, S)); });
         printf("check_s8 LP=%d m=%ld n=%ld: max|bf16 path - fp8 path| = %.3e (max %.3e); bf16->e4m3 code mismatches %zu;"
                " bf16 path %.1f us, fp8 path %.1f us (%.0f GB/s)\n", LP, (long)m, (long)n, md, mx, bad, t1, t2,
                bytes / t2 / 1e3);
@@ -683,8 +693,8 @@ static void check_s8() {
     CK(hipMalloc(&O, (size_t)m * LP * 4));
     CK(hipMalloc(&sl, (size_t)m * LP * 4));
     WProjPlan p = plan_wproj(m, n, LP, true, true, true);
-    double t1 = time_us([&] { CK(launch_wproj(1, 1, A, m, m, n, Sb, nullptr, LP, p, sl, O, S)); });
-    double t2 = time_us([&] { CK(launch_wproj_s8(A, m, m, n, reinterpret_cast<const fp8_t*>(S8), LP, p, sl, O, S)); });
+    double t1 = time_us([&] { CK(launch_wproj(A, m, m, n, Sb, nullptr, p, sl, O, S)); });
+    double t2 = time_us([&] { CK(launch_wproj_s8(A, m, m, n, reinterpret_cast<const fp8_t*>(S8), p, sl, O, S)); });
     const double fl = 2.0 * m * n * LP;
     printf("C5 sketch 131072x8192 e4m3, LP=512: bf16-MFMA path %.1f us (%.0f TF), fp8-MFMA path %.1f us (%.0f TF = %.3f "
            "of the 5033 TF fp8 dense peak), splits %d\n", t1, fl / t1 / 1e6, t2, fl / t2 / 1e6, fl / t2 / 1e6 / 5033.2,
@@ -800,9 +810,9 @@ int main(int argc, char** argv) {
             for (int kn = 0; kn < 4; ++kn) {
                 WProjPlan pn = plan_wproj(m, n, LP, true), pt = plan_wproj(n, m, LP, true, false, false);
                 pn.kn = pt.kn = kn;
-                double t0 = time_us([&] { CK(launch_wproj(1, 0, A, m, m, n, Sh, nullptr, LP, pn, nullptr, Out, S)); });
-                double t1 = time_us([&] { CK(launch_wproj(1, 0, A, m, m, n, Sh, Sl, LP, pn, nullptr, Out, S)); });
-                double t2 = time_us([&] { CK(launch_wproj(0, 0, A, m, m, n, Sh, Sl, LP, pt, nullptr, Out, S)); });
+                double t0 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, nullptr, pn, nullptr, Out, S)); });
+                double t1 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, Sl, pn, nullptr, Out, S)); });
+                double t2 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, Sl, pt, nullptr, Out, S)); });
                 printf("rep %d kn %d: NN1 %.1f us  NN2 %.1f us  TN2 %.1f us\n", rep, kn, t0, t1, t2);
             }
     }
@@ -820,8 +830,8 @@ int main(int argc, char** argv) {
         for (int ab = 0; ab < 8; ++ab) {
             WProjPlan pn = plan_wproj(m, n, LP, true), pt = plan_wproj(n, m, LP, true, false, false);
             pn.abl = pt.abl = ab;
-            double t1 = time_us([&] { CK(launch_wproj(1, 0, A, m, m, n, Sh, Sl, LP, pn, nullptr, Out, S)); });
-            double t2 = time_us([&] { CK(launch_wproj(0, 0, A, m, m, n, Sh, Sl, LP, pt, nullptr, Out, S)); });
+            double t1 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, Sl, pn, nullptr, Out, S)); });
+            double t2 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, Sl, pt, nullptr, Out, S)); });
             printf("abl %d (%s%s%s): NN2 %.1f us (%.0f TF)  TN2 %.1f us (%.0f TF)\n", ab, ab & 1 ? "nobar " : "",
                    ab & 2 ? "nodma " : "", ab & 4 ? "nolds" : "", t1, fl / t1 / 1e6, t2, fl / t2 / 1e6);
         }
@@ -847,21 +857,21 @@ int main(int argc, char** argv) {
                 float* slabs = nullptr;  // K-split partial products (p.splits > 1 writes them)
                 CK(hipMalloc(&slabs, (size_t)p0.splits * ro * LP * 4));
                 printf("case %ldx%ld nn %d splits %d ...\n", (long)m, (long)n, nn, p0.splits);
-                double t0 = time_us([&] { CK(launch_wproj(nn, 0, A, m, m, n, Sh, Sl, LP, p0, slabs, O0, S)); });
+                double t0 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, Sl, p0, slabs, O0, S)); });
                 printf("  dma-A %.1f us\n", t0);
-                double t1 = time_us([&] { CK(launch_wproj(nn, 0, A, m, m, n, Sh, Sl, LP, p1, slabs, O1, S)); });
+                double t1 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, Sl, p1, slabs, O1, S)); });
                 CK(hipFree(slabs));
                 std::vector<float> h0((size_t)ro * LP), h1((size_t)ro * LP);
                 CK(hipMemcpy(h0.data(), O0, h0.size() * 4, hipMemcpyDeviceToHost));
                 CK(hipMemcpy(h1.data(), O1, h1.size() * 4, hipMemcpyDeviceToHost));
                 const bool same = !memcmp(h0.data(), h1.data(), h0.size() * 4);
                 printf("areg %ldx%ld %s: dma-A %.1f us (%.0f TF)  reg-A %.1f us (%.0f TF)  bit-identical %d\n", (long)m,
-                       (long)n, nn ? "NN2" : (p0.tn2 ? "TN2(v3 tn2)" : "TN2(v3)"), t0, fl / t0 / 1e6, t1, fl / t1 / 1e6, (int)same);
+                       (long)n, nn ? "NN2" : (p0.kernel == WProjKernel::W3Tn2 ? "TN2(v3 tn2)" : "TN2(v3)"), t0, fl / t0 / 1e6, t1, fl / t1 / 1e6, (int)same);
             }
             CK(hipFree(A)); CK(hipFree(Sh)); CK(hipFree(Sl)); CK(hipFree(O0)); CK(hipFree(O1));
         }
     }
-    if (what == "tn128") {  // LP = 128 TN: v2 double-step stages (tn3 off) against the separate rings
+    if (what == "tn128") {  // LP = 128 TN: v2 double-step stages (W2Ds) against the separate rings
         for (int cs = 0; cs < 2; ++cs) {
             const int64_t m = cs ? (1 << 20) : 4160, n = cs ? 1024 : 1000;  // case 0: ragged rows, K chunks
             const int LP = 128;
@@ -874,23 +884,24 @@ int main(int argc, char** argv) {
             CK(hipMalloc(&O0, (size_t)n * LP * 4));
             CK(hipMalloc(&O1, (size_t)n * LP * 4));
             WProjPlan p0 = plan_wproj(n, m, LP, true, false, false), p1 = p0, p2 = p0;
-            p0.tn3 = 0;
-            p1.tn3 = p1.ds ? 1 : 0;
-            p2.tn3 = p2.ds ? 2 : 0;
+            // (m a multiple of 64 in both cases: the planner's double-step choice, whatever RSVD_TN128 says)
+            p0.kernel = WProjKernel::W2Ds;
+            p1.kernel = p2.kernel = WProjKernel::W3Tn128;
+            p2.rings33 = true;
             float* slabs;
             CK(hipMalloc(&slabs, (size_t)p0.splits * n * LP * 4));
             const double bytes = (double)m * n * 2;
             for (int sp = 1; sp >= 0; --sp) {
                 const bf16_t* lo = sp ? Sl : nullptr;
                 for (int rep = 0; rep < 2; ++rep) {
-                    double t0 = time_us([&] { CK(launch_wproj(0, 0, A, m, m, n, Sh, lo, LP, p0, slabs, O0, S)); });
+                    double t0 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, lo, p0, slabs, O0, S)); });
                     std::vector<float> h0((size_t)n * LP), h1((size_t)n * LP);
                     CK(hipMemcpy(h0.data(), O0, h0.size() * 4, hipMemcpyDeviceToHost));
-                    double t1 = time_us([&] { CK(launch_wproj(0, 0, A, m, m, n, Sh, lo, LP, p1, slabs, O1, S)); });
+                    double t1 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, lo, p1, slabs, O1, S)); });
                     CK(hipMemcpy(h1.data(), O1, h1.size() * 4, hipMemcpyDeviceToHost));
                     const bool same1 = !memcmp(h0.data(), h1.data(), h0.size() * 4);
                     CK(hipMemset(O1, 0, h1.size() * 4));
-                    double t2 = time_us([&] { CK(launch_wproj(0, 0, A, m, m, n, Sh, lo, LP, p2, slabs, O1, S)); });
+                    double t2 = time_us([&] { CK(launch_wproj(A, m, m, n, Sh, lo, p2, slabs, O1, S)); });
                     CK(hipMemcpy(h1.data(), O1, h1.size() * 4, hipMemcpyDeviceToHost));
                     const bool same2 = !memcmp(h0.data(), h1.data(), h0.size() * 4);
                     printf("tn128 %ldx%ld TN%d splits %d: v2ds %.1f us (%.0f GB/s)  rings 4/2 %.1f us (%.0f GB/s) same %d"
