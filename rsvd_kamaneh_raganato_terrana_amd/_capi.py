@@ -80,9 +80,10 @@ COLL_REDUCE_SCATTER, COLL_ALL_GATHER = 1, 2
 
 def _sources():
     """The files librsvd_hip.so is built from, in the order the Makefile hashes them."""
-    hip = "util.hip proj.hip qr.hip jacobi.hip wide_proj.hip wide_qr.hip wide_svd.hip wide_eig.hip dense.hip gemm.hip".split()
+    hip = ("util.hip proj.hip qr.hip jacobi.hip wide_proj.hip wide_gram.hip wide_chol.hip wide_panel.hip wide_svd.hip "
+           "wide_eig.hip dense.hip gemm.hip").split()
     cpp = "driver.cpp wide.cpp wide_plan.cpp dense_api.cpp comm.cpp dense_big.cpp".split()
-    hdr = "common.hpp kernels.hpp wide.hpp dense.hpp handle.hpp".split()
+    hdr = "common.hpp kernels.hpp wide.hpp wide_dev.hpp dense.hpp handle.hpp".split()
     return ([os.path.join(CSRC, f) for f in hip + cpp + hdr] + [os.path.join(REPO, "include", "rsvd_c.h")]
             + [os.path.join(CSRC, "Makefile")])
 

@@ -1,7 +1,7 @@
 // dense.hip -- kernels of the dense drop-ins next to rSVD: QR() (src/QR.cpp:22-80) and the
 // stand-alone SVD<method> (include/SVD_class.hpp:79-219).  The heavy lifting reuses the wide
-// engine's CholeskyQR / Gram / panel-product / Jacobi kernels (wide_qr.hip, wide_svd.hip,
-// jacobi.hip); this file adds the layout helpers and the power method.
+// engine's CholeskyQR / Gram / panel-product / Jacobi kernels (wide_gram.hip, wide_chol.hip,
+// wide_panel.hip, wide_svd.hip, jacobi.hip); this file adds the layout helpers and the power method.
 //
 //   transpose_to_panel   A (m x n col-major) -> A^T as an n x LP row-major panel: the panel row j
 //                        is column j of A, so reads and writes are both unit-stride.
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void qr_signs_kernel(const T* __restrict__ A, 
 
 // Out = In R^-1 by forward substitution per row (R upper, LP x LP fp64): q R = a solved row by
 // row is backward stable, |a - q R| <= O(u) |q| |R|, however ill-conditioned R is -- the explicit
-// R^-1 product of the rSVD panels (wide_qr.hip panel_gemm) loses u * cond(R), which a QR() caller
+// R^-1 product of the rSVD panels (wide_panel.hip panel_gemm) loses u * cond(R), which a QR() caller
 // would see as A != Q R for rank-deficient A.  One thread per row; the R columns of a 32-wide
 // chunk are staged in LDS (rows 0 .. c0 + 32), earlier outputs of the row are re-read from Out.
 template <typename T>

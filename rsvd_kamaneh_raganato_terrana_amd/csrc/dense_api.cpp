@@ -131,8 +131,10 @@ struct DenseEngine {
     int pass(const T* In, int k, T* Out, bool shift, const int* pred) {
         RSVD_CK(launch_gram_wide<T>(In, nullptr, L.rows, L.LP, L.gp, gslab, G, pred, s));
         if (shift) RSVD_CK(launch_shift_diag(G, L.LP, k, L.rows, sizeof(T) == 4 ? 0x1p-24 : 0x1p-53, s));
-        RSVD_CK(launch_chol_wide(G, k, L.LP, tol(), R, Rinv, sizeof(T) == 4 ? Rinv32 : nullptr, colflag, flag, W, pred,
-                                 s));
+        CholArgs a;
+        a.G = G, a.l = k, a.LP = L.LP, a.tol = tol(), a.R = R, a.Rinv = Rinv, a.Rinv32 = sizeof(T) == 4 ? Rinv32 : nullptr;
+        a.colflag = colflag, a.flag = flag, a.work = W, a.pred = pred;
+        RSVD_CK(launch_chol(a, s));
         // forward substitution rather than the R^-1 product: backward stable for ill-conditioned R
         RSVD_CK(launch_trsm_rows<T>(In, L.rows, k, L.LP, R, Out, pred, s));
         return RSVD_OK;

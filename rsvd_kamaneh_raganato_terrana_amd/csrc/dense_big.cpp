@@ -141,7 +141,10 @@ struct QrBig {
         RSVD_TRY(allreduce(G, (int64_t)LP * LP, RSVD_F64));
         if (shift)
             RSVD_CK(launch_shift_diag(G, LP, k, shard ? rows_global : rows, sizeof(T) == 4 ? 0x1p-24 : 0x1p-53, s));
-        RSVD_CK(launch_chol_wide(G, k, LP, tol(), R, Rinv, sizeof(T) == 4 ? R32 : nullptr, colflag, flag, W, pred, s));
+        CholArgs a;
+        a.G = G, a.l = k, a.LP = LP, a.tol = tol(), a.R = R, a.Rinv = Rinv, a.Rinv32 = sizeof(T) == 4 ? R32 : nullptr;
+        a.colflag = colflag, a.flag = flag, a.work = W, a.pred = pred;
+        RSVD_CK(launch_chol(a, s));
         RSVD_CK(launch_trsm_rows<T>(In, rows, k, LP, R, Out, pred, s));
         return RSVD_OK;
     }

@@ -327,18 +327,9 @@ struct WideEngine {
     // fp64 Gram and factor run again.
     static constexpr double kSplitIllTol = 1e-7;
     bool split_gram = false;
-    static constexpr int split_cross = 3;  // bits: 1 the split cross Gram at LP = 256, 2 at LP = 512
     bool split_panel = false;  // panel products on the bf16 MFMA, three-piece split (fp32 panels of bf16 / e4m3 A)
     bf16_t* Ms = nullptr;
     bf16_t* ms() const { return split_panel ? Ms : nullptr; }
-    // two-level factor: bit 0 at LP = 512, bit 1 at LP = 256 (0 would be one level
-    // everywhere).  Round 4 default 3: with the K-split 128^3 / 256^3 products (four waves per tile)
-    // and the DPP diagonal factor, tools/wide_lab chol: LP = 256 one level 157.8 us vs two levels
-    // 145.5 us; LP = 512 two levels 350.2 us vs three (each 256 level itself two-level) 321.8 us
-    static constexpr int chol2 = 3;
-    // LP = 512 with bit 1 also set: each 256-column level is itself two-level (three levels of 128)
-    int chol_depth() const { return (L.LP == 512 && (chol2 & 2)) ? 1 : 0; }
-    static constexpr int bj_groups = 0;  // block-Jacobi row groups (0: auto)
     bool eig_svd = true;  // fp32 results: the small SVD through the eigensolver (RSVD_SMALL_SVD=jacobi: block Jacobi)
     // panel_gemm's operand in the panel precision: fp64 matrices as-is, fp32 copies for fp32 panels
     const T* mat(const double* m64, const float* m32) const {
@@ -353,19 +344,24 @@ struct WideEngine {
     bool split_sharded = false;
     bool split_path(bool sharded, const int* pred) const { return split_gram && !pred && (!sharded || split_sharded); }
 
+    // The factor of G into Ro / Rio, breakdowns counted in fl: the fields every call shares.
+    CholArgs chol_args(double* Ro, double* Rio, int* fl) const {
+        CholArgs a;
+        a.G = G, a.l = L.l, a.LP = L.LP, a.tol = tol(), a.R = Ro, a.Rinv = Rio;
+        a.colflag = colflag, a.flag = fl, a.work = W;
+        return a;
+    }
+
     // R = chol(P^T P) and R^-1 (Ro, Rio; with the fp32 copy and bf16 pieces of R^-1 when r32 / mt).
     int gram_factor(const T* P, int64_t rows, const GramPlan& gp, bool sharded, int* flag, const int* pred, double* Ro,
                     double* Rio, float* r32, bf16_t* mt) {
-        // LP = 256 / 512, l > LP / 2: the two-level factor (wide_qr.hip launch_chol_wide_2level; JX is
-        // free scratch until the small SVD) for unpredicated passes
-        const bool two = (chol2 & (L.LP == 512 ? 1 : (L.LP == 256 ? 2 : 0))) && L.l > L.LP / 2;
-        auto factor = [&](int* fl, double ill_tol, int* ill) -> hipError_t {
-            if (two)
-                return launch_chol_wide_2level(G, L.l, L.LP, tol(), Ro, Rio, r32, colflag, fl, W, JX, s, ill_tol, ill,
-                                               nullptr, chol_depth(), mt);
-            return launch_chol_wide(G, L.l, L.LP, tol(), Ro, Rio, r32, colflag, fl, W, nullptr, s, ill_tol, ill,
-                                    nullptr, mt);
-        };
+        CholArgs a = chol_args(Ro, Rio, flag);
+        a.Rinv32 = r32, a.Mt = mt;
+        // unpredicated passes at LP >= 256: the two-level factor (wide_chol.hip; JX is free scratch until the
+        // small SVD), at LP = 512 each 256-column level itself two-level.  tools/wide_lab chol, round 4: LP = 256
+        // one level 157.8 us vs two 145.5 us; LP = 512 two levels 350.2 us vs three levels of 128 321.8 us
+        const int depth = L.LP >= 256 ? (L.LP == 512 ? 1 : 0) : -1;
+        a.scratch = JX;
         // sharded: the rank's Gram summed over the ranks (the first m-side sum carries the global row count)
         auto sum_ranks = [&]() -> int {
             if (!sharded) return RSVD_OK;
@@ -381,29 +377,29 @@ struct WideEngine {
             int* ill = h->dflags + kFlagSplitIll;
             RSVD_CK(launch_gram_split(reinterpret_cast<const float*>(P), rows, L.LP, gp, gslab, G, s));
             RSVD_TRY(sum_ranks());
-            RSVD_CK(factor(h->dflags + kFlagSplitScratch, kSplitIllTol, ill));
+            CholArgs t = a;  // the split Gram's factor: its breakdowns raise `ill`, not the pass's flag
+            t.flag = h->dflags + kFlagSplitScratch, t.ill_tol = kSplitIllTol, t.ill = ill, t.depth = depth;
+            RSVD_CK(launch_chol(t, s));
             RSVD_CK(launch_gram_wide<T>(P, nullptr, rows, L.LP, gp, gslab, G, ill, s));
             // sharded: the fallback Gram's sum is issued whether or not `ill` is raised (a device word the
             // host does not read; every rank factors the same summed G, so the ranks' words agree).  When
             // it is clear, G is dead and so is this sum.
             RSVD_TRY(sum_ranks());
-            RSVD_CK(launch_chol_wide(G, L.l, L.LP, tol(), Ro, Rio, r32, colflag, flag, W, ill, s, 0.0, nullptr, nullptr,
-                                     mt));
+            a.pred = ill;  // the fp64 factor runs only where the split one raised `ill`
+            RSVD_CK(launch_chol(a, s));
             return RSVD_OK;
         }
         RSVD_CK(launch_gram_wide<T>(P, nullptr, rows, L.LP, gp, gslab, G, pred, s));
         RSVD_TRY(sum_ranks());
-        if (pred)
-            RSVD_CK(launch_chol_wide(G, L.l, L.LP, tol(), Ro, Rio, r32, colflag, flag, W, pred, s, 0.0, nullptr, nullptr,
-                                     mt));
-        else
-            RSVD_CK(factor(flag, 0.0, nullptr));
+        a.pred = pred;
+        if (!pred) a.depth = depth;
+        RSVD_CK(launch_chol(a, s));
         return RSVD_OK;
     }
 
     // One CholeskyQR pass Out = P chol(P^T P)^-1 (+ bf16 hi/lo of Out).  `pred`: predicated pass.
     // fp32 panels of bf16 / e4m3 A (unpredicated passes, any world size): the Gram by the three-piece bf16
-    // split (wide_qr.hip gram_split_kernel, |dG| ~ 1e-8 |G|); when a pivot of its factor falls below
+    // split (wide_gram.hip gram_split_kernel, |dG| ~ 1e-8 |G|); when a pivot of its factor falls below
     // kSplitIllTol of its diagonal (cond(P) beyond ~1e3, or a breakdown) the fp64 Gram and factor
     // run again, predicated on that test (h->dflags[kFlagSplitIll]), and their R / R^-1 / flags stand.
     int cholqr_pass(const T* P, int64_t rows, const GramPlan& gp, T* Out, bool sharded, bf16_t* hi, bf16_t* lo,
@@ -464,8 +460,9 @@ struct WideEngine {
         // E = G - I and the cut-off test; past it the Cholesky factor (predicated), then G is scratch
         RSVD_CK(launch_isqrt_near_identity(G, L.l, L.LP, Mu, Mv, nullptr, nullptr, nullptr, nullptr, fl, s, true,
                                            false));
-        RSVD_CK(launch_chol_wide(G, L.l, L.LP, tol(), R2s, r2inv, nullptr, colflag, h->dflags + kFlagUnrepaired, W,
-                                 fl + 1, s, 0.0, nullptr, nullptr, nullptr));
+        CholArgs a = chol_args(R2s, r2inv, h->dflags + kFlagUnrepaired);
+        a.pred = fl + 1;  // the flag word the cut-off test raises
+        RSVD_CK(launch_chol(a, s));
         RSVD_CK(launch_isqrt_near_identity(nullptr, L.l, L.LP, Mu, Mv, Tmp, R2s, G, r2inv, fl, s, false, true));
         return RSVD_OK;
     }
@@ -585,7 +582,7 @@ struct WideEngine {
         } else {
             // R = Q_B^T B^T: fp32 panels of bf16 / e4m3 A at LP = 256 / 512 by the three-piece bf16 split
             // (the entries to ~1e-8 of |Q_B| |B^T|, as the split Grams; RSVD_GRAM_SPLIT=0: fp64 MFMA)
-            if (split_gram && ((L.LP == 256 && (split_cross & 1)) || (L.LP == 512 && (split_cross & 2))))
+            if (split_gram && (L.LP == 256 || L.LP == 512))
                 RSVD_CK(launch_gram_split_cross(reinterpret_cast<const float*>(Xn), reinterpret_cast<const float*>(Zn),
                                                 L.n, L.LP, L.gx, gslab, R1, s));
             else
@@ -611,10 +608,8 @@ struct WideEngine {
         } else {
             // fp32 results (fp32 / bf16 / e4m3 A): converged at cos <= 1e-6 -- 16 fp32 ulps, far below
             // the 1e-4 bar -- one or two sweeps fewer than the fp64 results' 1e-12
-            const int bjg = bj_groups > 0 && block_jacobi_groups(L.LP, L.LP, bj_groups) ? bj_groups : 0;
             RSVD_CK(launch_block_jacobi<double>(R1, L.l, L.LP, JX, JJ, Uw, Vw, Sd, sync, h->dflags + 1, s,
-                                                sizeof(T) == 4 ? 1e-8 : 1e-16, sizeof(T) == 4 ? kBJTolF32 : kBJTolF64,
-                                                bjg));
+                                                sizeof(T) == 4 ? 1e-8 : 1e-16, sizeof(T) == 4 ? kBJTolF32 : kBJTolF64));
         }
         // deferred: U = T1 (R2m^-1 U_w), V = T1z (R2n^-1 V_w)
         double* Uw = this->Uw;

@@ -77,7 +77,23 @@ hipError_t launch_wproj_s8(const void* A, int64_t lda, int64_t m, int64_t n, con
 // bf16 panel holding exactly-e4m3 values -> e4m3 codes (count elements)
 hipError_t launch_bf16_to_fp8(const bf16_t* in, int64_t count, fp8_t* out, hipStream_t s);
 
-// ---- wide_qr.hip -------------------------------------------------------------------------------
+// ---- tall-skinny orthonormalisation: wide_gram.hip, wide_chol.hip, wide_panel.hip ---------------
+// The reference takes a Householder thin Q of every tall-skinny panel (src/rSVD.cpp:60-61,
+// 64-65, 67-68); only span(Q) reaches the outputs.  Here: CholeskyQR(2) --
+//   G = P^T P            wide_gram.hip: fp64 MFMA (v_mfma_f64_16x16x4_f64), one workgroup per row chunk
+//                        reading its rows once, or the three-piece bf16 split on the bf16 MFMA, + a
+//                        fixed-order chunk reduction (deterministic);
+//   R = chol(G), R^-1    wide_chol.hip: ONE workgroup, 16-column blocks, fp64 MFMA trailing updates,
+//                        breakdown detection per pivot; two B-column levels of it at LP = 256 / 512;
+//   Q = P R^-1           wide_panel.hip: fp32 MFMA (fp64 for fp64 panels) or the bf16 split, that also
+//                        writes the bf16 hi/lo panels the next projection reads (wide_proj.hip) and, for
+//                        the final U = Q U_w / V = Q_B V_w, the caller's column-major matrix.
+// Rank deficiency (a pivot below tol * G_kk): R row k := e_k and column k is flagged; the
+// driver then replaces flagged columns by Philox Gaussian vectors and re-orthonormalises
+// (repair_kernel + one predicated CholeskyQR pass) -- an orthonormal basis completed like the
+// reference's Householder Q.
+
+// ---- wide_gram.hip -------------------------------------------------------------------------------
 struct GramPlan {
     int blocks;   // 32 x 32 blocks of the Gram (upper triangle, or all for a cross Gram)
     int chunks;   // row chunks
@@ -90,27 +106,6 @@ GramPlan plan_gram_wide(int64_t rows, int LP, int cross);
 template <typename T>
 hipError_t launch_gram_wide(const T* P, const T* P2, int64_t rows, int LP, const GramPlan& gp, double* slabs,
                             double* G, const int* pred, hipStream_t s);
-// R = chol(G[:l,:l]) (upper) and Rinv = R^-1, LP x LP fp64 zero-padded, one workgroup.  A pivot
-// d_k <= tol * G_kk (or not finite) is a breakdown: R row k := e_k, colflag[k] = 1, *flag += 1.
-// Also writes Rinv as fp32 when Rinv32 != nullptr.  `work`: LP x LP fp64.  `pred`: as above.
-// ill (nullable): set to 1 when a pivot d_k <= ill_tol * G_kk (else 0) -- the split-Gram fallback test.
-hipError_t launch_chol_wide(const double* G, int l, int LP, double tol, double* R, double* Rinv, float* Rinv32,
-                            int* colflag, int* flag, double* work, const int* pred, hipStream_t s,
-                            double ill_tol = 0.0, int* ill = nullptr, const double* d0src = nullptr,
-                            bf16_t* Mt = nullptr, int ldg = 0);  // ldg: G's row pitch (0: LP)
-// The same factor at LP = 2 B (B = 128, 256; l > B) in two B-column levels: R11 = chol(G11) and
-// S = G22 - R12^T R12 (R12 = R11^-T G12), the off-diagonal blocks R12 and Rinv12 = -Rinv11 R12 Rinv22
-// on a B^3 fp64 MFMA GEMM, breakdowns judged against the diagonal of G (d0src when this factor is
-// itself a level) as the one-level factor does.  The levels are the one-workgroup LP = B kernels,
-// or (depth > 0, B = 256) two-level factors themselves.  scratch: chol_2level_scratch_doubles.
-hipError_t launch_chol_wide_2level(const double* G, int l, int LP, double tol, double* R, double* Rinv,
-                                   float* Rinv32, int* colflag, int* flag, double* work, double* scratch,
-                                   hipStream_t s, double ill_tol = 0.0, int* ill = nullptr,
-                                   const double* d0src = nullptr, int depth = 0, bf16_t* Mt = nullptr,
-                                   int ldg = 0);  // ldg: G's row pitch (0: LP)
-// (Mt, both factors, with Rinv32: R^-1's fp32 copy also as split_mat_kernel's three bf16 piece
-// images, 3 LP^2 -- launch_panel_gemm's msplit with msplit_ready)
-size_t chol_2level_scratch_doubles(int LP, int depth);
 // G = P^T P of an fp32 panel by the three-piece bf16 split on the bf16 MFMA (fp32 chunk sums added
 // in fp64; |dG| ~ 1e-8 |G|) -- same plan / slab layout as launch_gram_wide.  LP in {128, 256, 512}.
 bool gram_split_ok(int LP);
@@ -121,9 +116,31 @@ hipError_t launch_gram_split(const float* P, int64_t rows, int LP, const GramPla
 constexpr int64_t kSplitCrossRows = 4096;
 hipError_t launch_gram_split_cross(const float* X, const float* Y, int64_t rows, int LP, const GramPlan& gp,
                                    double* slabs, double* G, hipStream_t s);
-// 1 (default): chol_reg_kernel for LP <= 128, chol_wide_kernel above; 0: chol_wide_kernel everywhere;
-// 2: also chol_reg_kernel at LP = 256 (lab A/B only).
-extern int chol_variant;
+
+// ---- wide_chol.hip -------------------------------------------------------------------------------
+// R = chol(G[:l,:l]) (upper) and Rinv = R^-1, LP x LP fp64 zero-padded.  A pivot d_k <= tol * G_kk (or
+// not finite) is a breakdown: R row k := e_k, colflag[k] = 1, *flag += 1.  One workgroup (chol_reg_kernel
+// at LP = 64 / 128, else chol_wide_kernel); with depth >= 0, LP = 2 B in {256, 512} and l > B, two
+// B-column levels: R11 = chol(G11), S = G22 - R12^T R12 (R12 = R11^-T G12), R12 and Rinv12 =
+// -Rinv11 R12 Rinv22 on a B^3 fp64 MFMA GEMM, breakdowns judged against the diagonal of G (d0src when
+// this factor is itself a level).  The levels are this factor with depth - 1 (LP = 512, depth 1: four
+// LP = 128 leaves).  The two-level form has no predicate: depth >= 0 with pred is hipErrorInvalidValue.
+struct CholArgs {
+    const double* G = nullptr; int ldg = 0;  // row pitch, 0: LP
+    int l = 0, LP = 0; double tol = 0.0;
+    double *R = nullptr, *Rinv = nullptr;
+    float* Rinv32 = nullptr; bf16_t* Mt = nullptr;  // fp32 copy of R^-1, its bf16 pieces (launch_panel_gemm's msplit)
+    int *colflag = nullptr, *flag = nullptr; double* work = nullptr;  // work: LP x LP fp64
+    const int* pred = nullptr;  // device word; 0 skips the factor
+    double ill_tol = 0.0; int* ill = nullptr;  // *ill := a pivot d_k <= ill_tol * G_kk (split-Gram fallback test)
+    const double* d0src = nullptr;
+    int depth = -1; double* scratch = nullptr;  // >= 0: two-level where it applies (chol_2level_scratch_doubles)
+    int lab_variant = 1;  // lab only: 0 chol_wide_kernel at every LP, 2 (RSVD_LAB) chol_reg_kernel also at LP = 256
+};
+hipError_t launch_chol(const CholArgs& a, hipStream_t s);
+size_t chol_2level_scratch_doubles(int LP, int depth);
+
+// ---- wide_panel.hip ------------------------------------------------------------------------------
 // Out (rows x LP) = In (rows x LP) * M (LP x LP, row-major, in the panel precision T; `upper`:
 // only k <= c of M is read).  Out may be null with ldo = 0 when only the hi / lo panels are wanted.
 // Out layouts: row-major panel (ldo = 0) or the caller's column-major matrix (first

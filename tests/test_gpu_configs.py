@@ -144,7 +144,7 @@ def test_lowp_intermediates_flag(engine):
 
 @pytest.mark.parametrize("decay,l", [(0.995, 128), (0.9, 128), (0.97, 256), (0.985, 512)])
 def test_split_gram_paths(engine, decay, l):
-    """The split Gram (wide_qr.hip gram_split_kernel, bf16 / e4m3 A): its factor is kept while every
+    """The split Gram (wide_gram.hip gram_split_kernel, bf16 / e4m3 A): its factor is kept while every
     pivot stays above kSplitIllTol of its diagonal (0.995^i: cond(Y) ~ 2 at l = 128), and the fp64
     Gram + factor re-run (predicated) past it (0.9^i over 2 l columns: sigma_l / sigma_1 ~ 1e-6;
     0.97^i at l = 256; 0.985^i at l = 512) -- both must meet the 1e-4 bar against the oracle."""

@@ -148,7 +148,7 @@ def test_fp8_decode_all_codes(engine):
 def test_wide_rank_deficient_is_orthonormal(engine, l, rank):
     """rank(A) < l: breakdown columns are completed (repair pass), U and V stay orthonormal and A
     is reconstructed exactly, as the reference's Householder Q would.  l = 512 runs the two-level
-    LP = 512 factor (wide_qr.hip launch_chol_wide_2level) with breakdowns in its first level
+    LP = 512 factor (wide_chol.hip launch_chol, depth 1) with breakdowns in its first level
     (rank 6) and only in its second (rank 300)."""
     torch = _torch()
     rng = np.random.default_rng(4)

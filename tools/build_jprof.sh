@@ -9,5 +9,5 @@ T=$(mktemp -d)
 /opt/rocm/bin/hipcc $F -I. -c ../../tools/wide_lab.cpp -o $T/wide_lab.o
 O=../../build/obj
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -o ../../tools/wide_lab_jprof $T/wide_lab.o $T/wide_svd.o $O/util.o $O/proj.o \
-  $O/qr.o $O/jacobi.o $O/wide_proj.o $O/wide_qr.o $O/dense.o $O/gemm.o
+  $O/qr.o $O/jacobi.o $O/wide_proj.o $O/wide_plan.o $O/wide_gram.o $O/wide_chol.o $O/wide_panel.o $O/dense.o $O/gemm.o
 rm -rf $T

@@ -208,7 +208,7 @@ static double* spd(int LP, int l) {  // G = X^T X + I with X random l x l
 }
 
 #ifdef RSVD_CHOL_PROF
-namespace rsvd { void chol_prof_dump(int LP); void chol_diag_bench(); }
+namespace rsvd { void chol_prof_dump(int LP, int variant); void chol_diag_bench(); }
 #endif
 static void bench_chol() {
 #ifdef RSVD_CHOL_PROF
@@ -228,13 +228,16 @@ static void bench_chol() {
         CK(hipMemset(fl, 0, 4));
         // A/B: the L2-resident chol_wide_kernel (variant 0) against the register-resident chol_reg_kernel (1)
         std::vector<double> hR0((size_t)LP * LP), hRi0((size_t)LP * LP);
-        rsvd::chol_variant = 0;
-        double t0 = time_us([&] { CK(launch_chol_wide(G, LP, LP, 1e-13, R, Ri, R32, cf, fl, W, nullptr, S)); });
+        CholArgs a;
+        a.G = G, a.l = LP, a.LP = LP, a.tol = 1e-13, a.R = R, a.Rinv = Ri, a.Rinv32 = R32;
+        a.colflag = cf, a.flag = fl, a.work = W;
+        a.lab_variant = 0;
+        double t0 = time_us([&] { CK(launch_chol(a, S)); });
         CK(hipMemcpy(hR0.data(), R, hR0.size() * 8, hipMemcpyDeviceToHost));
         CK(hipMemcpy(hRi0.data(), Ri, hRi0.size() * 8, hipMemcpyDeviceToHost));
-        rsvd::chol_variant = 2;
-        double t = time_us([&] { CK(launch_chol_wide(G, LP, LP, 1e-13, R, Ri, R32, cf, fl, W, nullptr, S)); });
-        rsvd::chol_variant = 1;
+        a.lab_variant = 2;
+        double t = time_us([&] { CK(launch_chol(a, S)); });
+        a.lab_variant = 1;
         // check R^T R = G and R Ri = I on the host
         std::vector<double> hR((size_t)LP * LP), hRi((size_t)LP * LP), hG((size_t)LP * LP);
         CK(hipMemcpy(hR.data(), R, hR.size() * 8, hipMemcpyDeviceToHost));
@@ -253,9 +256,7 @@ static void bench_chol() {
                 e2 += (s2 - (i == j)) * (s2 - (i == j));
             }
 #ifdef RSVD_CHOL_PROF
-        rsvd::chol_variant = LP == 512 ? 0 : 1;  // LP = 512 ran chol_wide_kernel
-        rsvd::chol_prof_dump(LP);
-        rsvd::chol_variant = 1;
+        rsvd::chol_prof_dump(LP, LP == 512 ? 0 : 1);  // LP = 512 ran chol_wide_kernel
 #endif
         const bool same = !memcmp(hR0.data(), hR.data(), hR.size() * 8) && !memcmp(hRi0.data(), hRi.data(), hRi.size() * 8);
         printf("chol LP=%d: wide %.1f us  reg %.1f us  bit-identical %d   |R^T R - G|/|G| = %.2e  |R Rinv - I| = %.2e\n", LP,
@@ -263,10 +264,8 @@ static void bench_chol() {
         for (int depth = 0; LP >= 256 && depth <= (LP == 512 ? 1 : 0); ++depth) {  // the two-level factor
             double* scr;
             CK(hipMalloc(&scr, chol_2level_scratch_doubles(LP, depth) * 8));
-            double t2 = time_us([&] {
-                CK(launch_chol_wide_2level(G, LP, LP, 1e-13, R, Ri, R32, cf, fl, W, scr, S, 0.0, nullptr, nullptr,
-                                           depth));
-            });
+            a.depth = depth, a.scratch = scr;
+            double t2 = time_us([&] { CK(launch_chol(a, S)); });
             CK(hipMemcpy(hR.data(), R, hR.size() * 8, hipMemcpyDeviceToHost));
             CK(hipMemcpy(hRi.data(), Ri, hRi.size() * 8, hipMemcpyDeviceToHost));
             double f1 = 0, f2 = 0;
