@@ -188,7 +188,10 @@ typedef struct {
 } rsvd_timing_t;
 int rsvd_set_timing(rsvd_handle_t h, int enable);
 int rsvd_get_timing(rsvd_handle_t h, rsvd_timing_t *t);
-/* Use caller-owned device memory as the workspace (NULL reverts to handle-owned memory). */
+/* Use caller-owned device memory as the workspace (NULL reverts to handle-owned memory).
+ * The workspace's contents are unspecified on entry and on return: every run initialises what it
+ * reads, no state is carried in the workspace between runs, and results do not depend on what it
+ * held before (tests/test_gpu_workspace.py runs every engine over 0x00 / 0xFF / 0x4B fills). */
 int rsvd_set_workspace(rsvd_handle_t h, void *ptr, size_t bytes);
 
 /* ---- device-pointer entry points (asynchronous on the handle stream) ---------------------- */

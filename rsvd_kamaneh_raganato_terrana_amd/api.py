@@ -214,6 +214,11 @@ class Engine:
             check(lib().rsvd_set_workspace(self.h, ctypes.c_void_p(self._ws.data_ptr()), nbytes), self.h)
         return self._ws
 
+    def workspace(self):
+        """The handle's current workspace as a uint8 CUDA tensor, or None before the first
+        reservation.  Its contents are unspecified between runs (include/rsvd_c.h)."""
+        return self._ws
+
     def set_comm(self, rank: int, world: int, group=None, shard_n: bool = True):
         """Row-sharded runs: bind the exchange hooks to torch.distributed over RCCL -- the
         all-reduce (m-side Grams; A^T Q when the n side is replicated) and, with shard_n, the

@@ -377,6 +377,16 @@ __global__ __launch_bounds__(kPowThreads) void power_svd_kernel(const T* __restr
             for (int c = tid; c < n; c += kPowThreads) Vr[(int64_t)c * LP + i] = 0.0;
             if (tid == 0) S[i] = 0.0;
         }
+        // rSVD mode: U_p and V_c are LP x LP small matrices (m = n = l) that multiply whole LP-wide
+        // panels afterwards -- their padding (rows past l, columns past dim) is written here, not left
+        // to what the workspace held
+        if (m <= LP) {
+            for (int e = tid; e < LP * LP; e += kPowThreads) {
+                const int r = e / LP, c = e % LP;
+                if (r >= m || c >= dim) Up[e] = T(0);
+                if (r >= n || c >= dim) Vr[e] = 0.0;
+            }
+        }
     }
     if (tid == 0) *kept = k;
 }
@@ -802,12 +812,17 @@ __global__ __launch_bounds__(kPjThreads) void pjacobi_ref_kernel(const TI* __res
     __shared__ int cnt_s, skip_s[2], flag_s;  // skip_s double-buffered: thread 0 writes the next
                                               // one while slower waves still read this one
     const int tid = threadIdx.x;
-    for (int e = tid; e < d * d; e += kPjThreads) {
-        const int p = e / d, q = e % d;
-        const bool zero = (tri > 0 && p > q) || (tri < 0 && p < q);  // the triangle's exact zeros
-        W[(int64_t)p * LP + q] = zero ? 0.0 : (double)Win[(int64_t)p * sp + (int64_t)q * sq];
-        Jl[(int64_t)p * LP + q] = (p == q) ? 1.0 : 0.0;
-        Jr[(int64_t)p * LP + q] = (p == q) ? 1.0 : 0.0;
+    // Jl / Jr over the whole LP x LP (zero past d: the callers multiply whole LP-wide panels by them, and
+    // the workspace they live in holds anything on entry); W only where it is read
+    for (int e = tid; e < LP * LP; e += kPjThreads) {
+        const int p = e / LP, q = e % LP;
+        const bool in = p < d && q < d;
+        if (in) {
+            const bool zero = (tri > 0 && p > q) || (tri < 0 && p < q);  // the triangle's exact zeros
+            W[(int64_t)p * LP + q] = zero ? 0.0 : (double)Win[(int64_t)p * sp + (int64_t)q * sq];
+        }
+        Jl[(int64_t)p * LP + q] = (in && p == q) ? 1.0 : 0.0;
+        Jr[(int64_t)p * LP + q] = (in && p == q) ? 1.0 : 0.0;
     }
     __syncthreads();
     if (tid == 0) {

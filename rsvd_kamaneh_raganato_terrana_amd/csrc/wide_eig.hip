@@ -697,6 +697,10 @@ __global__ __launch_bounds__(64) void tridiag_invit_kernel(const double* __restr
         yc = ycn;
     }
     U0i[at(n - 1)] = pivot_inv(cd);
+    // the last row has no super-diagonals: the back substitution reads them (times z = 0) all the same,
+    // and the scratch holds whatever the workspace held -- 0 x NaN is NaN
+    U1[at(n - 1)] = 0.0;
+    U2[at(n - 1)] = 0.0;
     INV_TS(4);
     X[at(n - 1)] = yc;
     // back substitution U z = y (z into X): max |z| and sum z^2.  The operands are read in chunks of

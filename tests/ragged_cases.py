@@ -208,6 +208,8 @@ CASES = [
     _c("f32e", "f32", 1003, 771, 200, 2, dict(engine="wide-fp", LP=256), (6, 1)),
     _c("f32f", "f32", 150, 140, 130, 1, dict(engine="wide-fp", LP=192), (1, 1)),
     _c("f64a", "f64", 601, 403, 65, 1, dict(engine="wide-fp", LP=128), (3, 2)),
+    # the narrow engine in fp64 (f32a's shape): two 8-byte lanes per 16-byte load, so TN splits too
+    _c("f64n", "f64", 513, 257, 10, 1, dict(engine="narrow", LP=16), (2, 2)),
 ]
 BY_ID = {c.id: c for c in CASES}
 

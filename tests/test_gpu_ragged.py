@@ -9,9 +9,9 @@ a. Every case against the fp64 oracle on the exact values the GPU sees, with the
 b. A's own pitch and base (bf16 and e4m3 views off the 16-byte chunk), against the oracle.
 c. Output and Omega pitch and base: bit identity with the dense run, every padding element and
    both guard columns still holding their prefill pattern; the same for the range finder's Q.
-Measured on an MI355X: the 54 tests of this file take 25 s together, the CPU oracle of the four
-l = 512 cases most of it (each oracle result is computed once and shared).  Every test prints its
-figures ("RAGGED <case>: ...") before asserting.
+Measured on an MI355X: the 54 tests of this file before the f64n row took 25 s together, the CPU
+oracle of the four l = 512 cases most of it (each oracle result is computed once and shared).
+Every test prints its figures ("RAGGED <case>: ...") before asserting.
 
 Measured relative Frobenius errors against the oracle (S, leading-half U, leading-half V), all 54
 tests passing; the branch each case reaches is in ragged_cases.CASES:
@@ -25,7 +25,7 @@ tests passing; the branch each case reaches is in ragged_cases.CASES:
   eLP   1.0e-6 9.7e-6 9.4e-6 | bLM   4.0e-7 1.3e-5 1.3e-5 | bLN   7.3e-7 8.7e-6 8.5e-6
   f32a  7.4e-8 6.1e-7 4.4e-7 | f32b  1.0e-7 3.6e-6 2.4e-6 | f32c  2.6e-7 2.7e-5 2.6e-5
   f32d  2.2e-8 4.0e-7 4.3e-7 | f32e  2.5e-8 7.6e-7 7.9e-7 | f32f  3.8e-8 1.0e-6 1.0e-6
-  f64a  5.9e-15 3.6e-14 3.5e-14
+  f64a  5.9e-15 3.6e-14 3.5e-14 | f64n  1.3e-15 1.3e-15 1.1e-15
   A views: b_base2 / b_lda1 / b_lda3 4.1e-7 3.4e-6 3.3e-6 | e_base1 / e_lda8 3.7e-7 9.6e-6 9.5e-6
 The largest orthonormality defect is f32c's U, 1.2e-4 (fp32 narrow engine at LP 64, bound 1e-3 as
 test_c2_full_size_f32); every other case stays below 3.4e-5.

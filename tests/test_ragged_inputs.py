@@ -8,8 +8,9 @@
   fp32-sized relative perturbation.  Required: leading-half U and V within 1e-5 relative Frobenius
   (10x inside the bar), S within 1e-6 (100x inside) and S[l/2 - 1] >= 10 S[l - 1].  A case that fails
   gets another decay / seed / weights in the table, never a shorter comparison.
-  Measured: the screen takes about 50 s for the 31 cases (the four l = 512 cases 8 - 9 s each, two
-  oracle runs of 4 s; the others 2 s or less), the whole file about 55 s.
+  Measured: the screen takes about 50 s for the 31 cases before the f64n row, which adds under a
+  second (the four l = 512 cases 8 - 9 s each, two oracle runs of 4 s; the others 2 s or less), the
+  whole file about 55 s.
 * The builder's point, oracle alone: a dropped last row or column of A moves S by > 1e-2.
 """
 import numpy as np
@@ -23,7 +24,7 @@ IDS = [c.id for c in rc.CASES]
 
 
 def test_table_shape():
-    assert len(set(IDS)) == len(IDS) == 31
+    assert len(set(IDS)) == len(IDS) == 32
     assert sorted(c.id for c in rc.CASES if c.l == 512) == ["b512f", "b512v", "e512f", "e512n"]
     for c in rc.CASES:
         assert c.l <= min(c.m, c.n) and c.q >= 1  # legal under check_desc_msg; q >= 1 runs NN hi / lo and TN
