@@ -420,37 +420,60 @@ class Engine:
         self._reserve_bytes(nbytes.value)
         self._bind_stream()
 
-    def qr(self, A, full: bool = False):
-        """Device QR of A (CUDA f64/f32): (Q, R), reduced (m x n, n x n) or full (m x m, m x n)."""
+    @staticmethod
+    def _check_out(X, rows: int, cols: int, dtype, what: str):
+        """out= matrices as range_finder's: column-major rows x cols of the result dtype, any leading
+        dimension >= rows (a one-column matrix may carry any column stride)."""
+        if (X.dim() != 2 or tuple(X.shape) != (rows, cols) or X.dtype != dtype or (rows > 1 and X.stride(0) != 1)
+                or (cols > 1 and X.stride(1) < rows)):
+            raise ValueError(f"out: {what} must be a column-major {rows} x {cols} matrix of the result dtype")
+        return max(X.stride(1), rows, 1)
+
+    def qr(self, A, full: bool = False, out=None):
+        """Device QR of A (CUDA f64/f32): (Q, R), reduced (m x n, n x n) or full (m x m, m x n).
+        out: (Q, R) column-major tensors to write into (any leading dimensions >= their rows)."""
         A, lda = colmajor(A)
         dt = self.abi_dtype(A.dtype)
         m, n = A.shape
         kq = m if full else n
+        if out is None:
+            Q = empty_colmajor(m, kq, A.dtype, A.device)
+            R = empty_colmajor(kq, n, A.dtype, A.device)
+        else:
+            Q, R = out
+        ldq = self._check_out(Q, m, kq, A.dtype, "Q")
+        ldr = self._check_out(R, kq, n, A.dtype, "R")
         self._reserve_dense(lib().rsvd_qr_workspace_bytes, m, n, dt, full)
-        Q = empty_colmajor(m, kq, A.dtype, A.device)
-        R = empty_colmajor(kq, n, A.dtype, A.device)
-        check(lib().rsvd_qr(self.h, m, n, ctypes.c_void_p(A.data_ptr()), lda, dt, int(full),
-                            ctypes.c_void_p(Q.data_ptr()), Q.stride(1), ctypes.c_void_p(R.data_ptr()),
-                            max(1, R.stride(1))), self.h)
+        check(lib().rsvd_qr(self.h, m, n, ctypes.c_void_p(A.data_ptr()), max(lda, m), dt, int(full),
+                            ctypes.c_void_p(Q.data_ptr()), ldq, ctypes.c_void_p(R.data_ptr()), ldr), self.h)
         self.sync()
         return Q, R
 
-    def svd(self, A, method: int = SVDMethod.Jacobi, r: int = 0, seed: int = 0):
+    def svd(self, A, method: int = SVDMethod.Jacobi, r: int = 0, seed: int = 0, out=None):
         """Device SVD<method> of A (CUDA): (U m x k, S k, V n x k), k = min(m, n) (Power: the
-        triplets kept; V's columns are the right singular vectors)."""
+        triplets kept; V's columns are the right singular vectors).  out: (U m x k, S k, V n x k)
+        to write into, U and V column-major with any leading dimensions >= their rows, S with unit
+        stride; the views of the triplets kept are returned."""
         torch = _torch()
         A, lda = colmajor(A)
         dt = self.abi_dtype(A.dtype)
         m, n = A.shape
         k = min(m, n)
+        if out is None:
+            U = empty_colmajor(m, k, A.dtype, A.device)
+            S = torch.empty(k, dtype=A.dtype, device=A.device)
+            V = empty_colmajor(n, k, A.dtype, A.device)
+        else:
+            U, S, V = out
+            if S.dim() != 1 or S.shape[0] != k or S.dtype != A.dtype or (k > 1 and S.stride(0) != 1):
+                raise ValueError(f"out: S must be a unit-stride vector of {k} elements of the result dtype")
+        ldu = self._check_out(U, m, k, A.dtype, "U")
+        ldv = self._check_out(V, n, k, A.dtype, "V")
         self._reserve_dense(lib().rsvd_svd_workspace_bytes, m, n, dt, method)
-        U = empty_colmajor(m, k, A.dtype, A.device)
-        S = torch.empty(k, dtype=A.dtype, device=A.device)
-        V = empty_colmajor(n, k, A.dtype, A.device)
         kept = ctypes.c_int32(0)
-        check(lib().rsvd_svd(self.h, m, n, ctypes.c_void_p(A.data_ptr()), lda, dt, int(method), r, seed,
-                             ctypes.c_void_p(U.data_ptr()), U.stride(1), ctypes.c_void_p(S.data_ptr()),
-                             ctypes.c_void_p(V.data_ptr()), V.stride(1), ctypes.byref(kept)), self.h)
+        check(lib().rsvd_svd(self.h, m, n, ctypes.c_void_p(A.data_ptr()), max(lda, m), dt, int(method), r, seed,
+                             ctypes.c_void_p(U.data_ptr()), ldu, ctypes.c_void_p(S.data_ptr()),
+                             ctypes.c_void_p(V.data_ptr()), ldv, ctypes.byref(kept)), self.h)
         self.sync()
         kk = kept.value
         return U[:, :kk], S[:kk], V[:, :kk]

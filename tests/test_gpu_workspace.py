@@ -14,7 +14,9 @@ a. test_results_do_not_depend_on_workspace: per case one sizing run, then runs o
    _bounds, imported unchanged) and the splits of the table (the option cases change the algorithm,
    not the layout: identity and finiteness only); the three cases past 512 columns are held to
    finiteness and the orthonormality bounds of test_gpu_big_l.py / test_gpu_dense.py instead of the
-   oracle.  Every case prints "WS <case> <pattern>: identical" or the first differing index and the
+   oracle; the four rows of tests/dense_cases.py with padding columns inside LP (Power 90 x 70 in LP
+   80, Jacobi 131 x 65 in LP 96, fp32 Jacobi 65 x 131, fp32 QR 517 x 513: all bit-identical on every
+   pattern, 2.5 s together) are held to test_gpu_dense_ragged.py's reference check.  Every case prints "WS <case> <pattern>: identical" or the first differing index and the
    largest difference before asserting.
    test_nshard_layout_does_not_depend_on_workspace: the same on the n-side sharded layout at world
    1 (b128v: n = 702 in nfull = 704 rows), in one spawned child as test_gpu_rccl.py's library mode.
@@ -286,6 +288,20 @@ def _big_rsvd(engine):
     return (lambda: engine.rsvd(A, l, q=1, seed=514)), check
 
 
+def _dense_case(cid):
+    """A row of tests/dense_cases.py on the device path (Engine.qr / Engine.svd, the row's storage
+    dtype), held to test_gpu_dense_ragged.py's reference check."""
+    def make(engine):
+        import dense_cases as dc
+        from test_gpu_dense_ragged import _check_qr, _check_svd, _dev_A, _run
+
+        c = dc.BY_ID[cid]
+        A, _ = _dev_A(c, dc.inputs(cid))
+        check = _check_qr if c.op in ("qr", "qrfull") else _check_svd
+        return (lambda: _run(engine, c, A)), (lambda res: check(c, *(x.astype(np.float64) for x in res)))
+    return make
+
+
 def _methods():
     from rsvd_kamaneh_raganato_terrana_amd.api import QRMode, SVDMethod
 
@@ -324,6 +340,11 @@ def _cases():
         ("big-qr-600x513", _qr(600, 513, False, 600 * 3 + 513, orth=1e-12)),
         ("big-jacobi-600x513", _svd(600, 513, 0, sig=0.99 ** np.arange(513), mseed=600 + 2 * 513, orth=1e-12)),
         ("big-rsvd-700x600-l513", _big_rsvd),
+        # padding columns inside LP that had not yet run under the 0xFF fill (tests/dense_cases.py)
+        ("dense-power-90x70", _dense_case("power-f64-90x70-r8")),         # LP 80: gram_wide's half-empty block
+        ("dense-jacobi-131x65", _dense_case("jacobi-f64-131x65")),        # LP 96
+        ("dense-jacobi-65x131-f32", _dense_case("jacobi-f32-65x131")),    # LP 96, transpose_to_panel<float>
+        ("dense-qr-517x513-f32", _dense_case("qr-f32-517x513")),          # a one-column block in LP 512
     ]
     return cases
 
