@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RSVD_ABI_VERSION 6
+#define RSVD_ABI_VERSION 7
 
 typedef enum {
     RSVD_OK = 0,
@@ -245,6 +245,46 @@ int rsvd_svd(rsvd_handle_t h, int64_t m, int64_t n, const void *A, int64_t lda, 
 /* Device workspace bytes of rsvd_qr / rsvd_svd (for rsvd_set_workspace callers). */
 int rsvd_qr_workspace_bytes(int64_t m, int64_t n, int32_t dtype, int32_t full, size_t *bytes);
 int rsvd_svd_workspace_bytes(int64_t m, int64_t n, int32_t dtype, int32_t method, size_t *bytes);
+
+/* ---- batched rSVD (ABI 7): many small matrices, or the tiles of one large matrix ----------- */
+
+/* A batch of count0 * count1 matrices that share one rsvd_desc_t (m, n, lda, l, q, dtype, method,
+ * seed, a_scale).  Matrix b = i0 + count0 * i1 starts at A + i0 * a_stride0 + i1 * a_stride1
+ * (elements; the matrices may overlap) and writes U + b * u_stride, S + b * s_stride, V + b * v_stride.
+ * A plain strided batch is count1 = 1.  The tm x tn tiles of a column-major m x n matrix (the block
+ * decomposition of image_compression/src/image_com.cpp:350-371) are count0 = m / tm, a_stride0 = tm,
+ * count1 = n / tn, a_stride1 = tn * lda with desc->m = tm, desc->n = tn. */
+typedef struct {
+    int64_t count0, count1;        /* batch = count0 * count1 matrices; matrix b = i0 + count0 * i1 */
+    int64_t a_stride0, a_stride1;  /* elements: A_b = A + i0 * a_stride0 + i1 * a_stride1 (>= 0; may overlap) */
+    int64_t omega_stride;          /* elements between Omega_b and Omega_b+1; 0 = one Omega shared by all */
+    int64_t u_stride, s_stride, v_stride; /* elements between consecutive U_b / S_b / V_b (no overlap) */
+} rsvd_batch_t;
+
+/* Entry b is the rSVD rsvd_run computes on matrix b with seed desc->seed + b (omega == NULL: matrix b
+ * draws Philox(desc->seed + b), the Omega of rsvd_generate_omega(n, l, seed + b, dtype)); U_b, S_b, V_b
+ * are column-major with ldu / ldv as rsvd_run's.  Asynchronous on the handle's stream.
+ * Fused path (rsvd_batched_is_fused == 1: dtype F64 / F32, l <= 64, l <= min(m, n), max(m, n) <= 256,
+ * Jacobi / ParallelJacobi, qr_mode AUTO): ONE launch, one workgroup per matrix, A read in place (any
+ * base and lda), panels orthonormalised by Householder reflectors, so rank-deficient matrices (zero
+ * or constant tiles) come back with orthonormal U, V and zero trailing S like any other.  A matrix's
+ * result depends only on its own inputs.  Everything else rsvd_run accepts (any dtype, l <= 4096,
+ * larger matrices) loops rsvd_run over the sub-pointers on the same stream.
+ * info (nullable, device, 2 words per matrix): info[2b] = Jacobi sweeps, info[2b + 1] bit 0 = a
+ * rank-deficient sketch was met (looped path: the CGS2 repair ran), bit 1 = non-finite S.  On the
+ * looped path a non-NULL info costs one synchronisation per matrix.  Non-finite S in any matrix
+ * raises the handle's sticky word (rsvd_sync -> RSVD_ERR_NUMERICAL); the other matrices stay valid.
+ * RSVD_ERR_INVALID_ARG: counts < 1, a negative stride, an output stride below its output (ldu * l,
+ * l, ldv * l), ldu < m, ldv < n, flags != 0.  RSVD_ERR_UNSUPPORTED: a row-sharded handle (world > 1),
+ * RSVD_SVD_POWER / RSVD_SVD_POWER_IC. */
+int rsvd_run_batched(rsvd_handle_t h, const rsvd_desc_t *desc, const rsvd_batch_t *batch, const void *A,
+                     const void *omega, int64_t ldo, void *U, int64_t ldu, void *S, void *V, int64_t ldv,
+                     int32_t *info /* nullable, device, 2 per matrix */);
+/* Device workspace bytes of rsvd_run_batched (leading dimensions unknown: ldu = m, ldv = n assumed
+ * for the stride checks). */
+int rsvd_batched_workspace_bytes(const rsvd_desc_t *desc, const rsvd_batch_t *batch, size_t *bytes);
+/* Host-only: 1 when the description takes the fused kernel, 0 when it loops (or is invalid). */
+int rsvd_batched_is_fused(const rsvd_desc_t *desc, const rsvd_batch_t *batch);
 
 /* ---- host-pointer fp64 entry points used by the C++ drop-in headers (synchronous) --------- */
 int rsvd_run_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, int64_t lda, int32_t l,

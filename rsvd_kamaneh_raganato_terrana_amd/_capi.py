@@ -42,6 +42,7 @@ EXPORTS = (
     "rsvd_generate_omega_host_f64", "rsvd_qr", "rsvd_svd", "rsvd_qr_workspace_bytes",
     "rsvd_svd_workspace_bytes", "rsvd_qr_host_f64", "rsvd_svd_host_f64",
     "rsvd_comm_unique_id", "rsvd_comm_init", "rsvd_comm_destroy",
+    "rsvd_run_batched", "rsvd_batched_workspace_bytes", "rsvd_batched_is_fused",
 )
 
 
@@ -70,6 +71,15 @@ class Timing(ctypes.Structure):
     ]
 
 
+class BatchDesc(ctypes.Structure):
+    """rsvd_batch_t (include/rsvd_c.h, ABI 7): counts and element strides of a batch of matrices."""
+    _fields_ = [
+        ("count0", ctypes.c_int64), ("count1", ctypes.c_int64),
+        ("a_stride0", ctypes.c_int64), ("a_stride1", ctypes.c_int64), ("omega_stride", ctypes.c_int64),
+        ("u_stride", ctypes.c_int64), ("s_stride", ctypes.c_int64), ("v_stride", ctypes.c_int64),
+    ]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                 ctypes.c_void_p, ctypes.c_void_p)
 # rsvd_collective_fn(op, send, recv, count, dtype, stream, user) -- ABI 5
@@ -81,9 +91,9 @@ COLL_REDUCE_SCATTER, COLL_ALL_GATHER = 1, 2
 def _sources():
     """The files librsvd_hip.so is built from, in the order the Makefile hashes them."""
     hip = ("util.hip proj.hip qr.hip jacobi.hip wide_proj.hip wide_gram.hip wide_chol.hip wide_panel.hip wide_svd.hip "
-           "wide_eig.hip dense.hip gemm.hip").split()
-    cpp = "driver.cpp wide.cpp wide_plan.cpp dense_api.cpp comm.cpp dense_big.cpp".split()
-    hdr = "common.hpp kernels.hpp wide.hpp wide_dev.hpp dense.hpp handle.hpp".split()
+           "wide_eig.hip dense.hip gemm.hip batched.hip").split()
+    cpp = "driver.cpp wide.cpp wide_plan.cpp dense_api.cpp comm.cpp dense_big.cpp batched_run.cpp".split()
+    hdr = "common.hpp kernels.hpp wide.hpp wide_dev.hpp dense.hpp handle.hpp batched.hpp".split()
     return ([os.path.join(CSRC, f) for f in hip + cpp + hdr] + [os.path.join(REPO, "include", "rsvd_c.h")]
             + [os.path.join(CSRC, "Makefile")])
 
@@ -171,6 +181,10 @@ def lib():
     L.rsvd_comm_unique_id.argtypes = [vp]
     L.rsvd_comm_init.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.rsvd_comm_destroy.argtypes = [vp]
+    bp = ctypes.POINTER(BatchDesc)
+    L.rsvd_run_batched.argtypes = [vp, ctypes.POINTER(Desc), bp, vp, vp, i64, vp, i64, vp, vp, i64, vp]
+    L.rsvd_batched_workspace_bytes.argtypes = [ctypes.POINTER(Desc), bp, szp]
+    L.rsvd_batched_is_fused.argtypes = [ctypes.POINTER(Desc), bp]
     _LIB = L
     return L
 

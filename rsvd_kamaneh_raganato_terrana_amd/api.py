@@ -344,6 +344,122 @@ class Engine:
             self.sync()
         return U, S, V
 
+    # -- batched rSVD (rsvd_run_batched, include/rsvd_c.h ABI 7) ---------------------------------
+    def batched_is_fused(self, m: int, n: int, l: int, dtype, q: int = 2, method: int = SVDMethod.Jacobi,
+                         qr_mode: int = QRMode.Auto, batch: int = 1) -> int:
+        """rsvd_batched_is_fused: 1 when a batch of m x n matrices of this dtype (a torch dtype or an
+        ABI code) takes the fused one-launch kernel, 0 when rsvd_run_batched loops rsvd_run."""
+        dt = dtype if isinstance(dtype, int) else self.abi_dtype(dtype)
+        d = Desc(m=m, n=n, lda=m, l=l, q=q, dtype=dt, method=int(method), qr_mode=int(qr_mode), flags=0, seed=0,
+                 a_scale=1.0)
+        bd = _capi.BatchDesc(count0=batch, count1=1, a_stride0=m * n, a_stride1=0, omega_stride=0,
+                             u_stride=m * l, s_stride=l, v_stride=n * l)
+        return int(lib().rsvd_batched_is_fused(ctypes.byref(d), ctypes.byref(bd)))
+
+    def _run_batched(self, d: Desc, bd, A, omega, U, S, V, ldu: int, ldv: int, return_info: bool, check_errors: bool):
+        """Reserve, bind the stream and enqueue one rsvd_run_batched.  omega: None, (n, l) shared or
+        (B, n, l); it is brought to the result dtype, every matrix column-major."""
+        torch = _torch()
+        odt = self.out_dtype(A.dtype)
+        batch = bd.count0 * bd.count1
+        om_ptr, ldo = 0, 0
+        om = None
+        if omega is not None:
+            om = omega.to(device=A.device, dtype=odt)
+            if om.dim() == 2:
+                om, ldo = colmajor(om)
+                bd.omega_stride = 0
+            elif om.dim() == 3 and om.shape[0] == batch:
+                if not (om.stride(1) == 1 and om.stride(2) >= max(1, om.shape[1])):
+                    om = om.transpose(1, 2).contiguous().transpose(1, 2)
+                ldo = om.stride(2)
+                bd.omega_stride = om.stride(0) if batch > 1 else 0
+            else:
+                raise ValueError("omega must be (n, l) or (batch, n, l)")
+            if tuple(om.shape[-2:]) != (d.n, d.l):
+                raise ValueError("omega must have n rows and l columns")
+            om_ptr = om.data_ptr()
+        nbytes = ctypes.c_size_t(0)
+        check(lib().rsvd_batched_workspace_bytes(ctypes.byref(d), ctypes.byref(bd), ctypes.byref(nbytes)))
+        self._reserve_bytes(nbytes.value)
+        self._bind_stream()
+        info = torch.zeros((batch, 2), dtype=torch.int32, device=A.device) if return_info else None
+        check(lib().rsvd_run_batched(self.h, ctypes.byref(d), ctypes.byref(bd), ctypes.c_void_p(A.data_ptr()),
+                                     ctypes.c_void_p(om_ptr), ldo, ctypes.c_void_p(U.data_ptr()), ldu,
+                                     ctypes.c_void_p(S.data_ptr()), ctypes.c_void_p(V.data_ptr()), ldv,
+                                     ctypes.c_void_p(info.data_ptr() if info is not None else 0)), self.h)
+        if check_errors:
+            self.sync()
+        return info
+
+    def rsvd_batched(self, A, l: int, q: int = 2, method: int = SVDMethod.Jacobi, omega=None, seed: int = 0,
+                     out=None, return_info: bool = False, check_errors: bool = True, a_scale: float = 1.0):
+        """rSVD of every matrix of a CUDA tensor A (B, m, n): U (B, m, l), S (B, l), V (B, n, l) in
+        out_dtype(A.dtype), each matrix column-major.  Entry b is rsvd(A[b], l, q, seed=seed + b).
+
+        Each A[b] is used in place when it is column-major (stride(1) == 1, stride(2) >= m, any
+        stride(0)); any other layout gets one copy into that layout.  Small fp64 / fp32 matrices
+        (batched_is_fused) run in ONE launch, one workgroup per matrix; everything else loops rsvd.
+        omega: (n, l) shared by all, or (B, n, l).  return_info adds an int32 (B, 2) tensor: Jacobi
+        sweeps, and bit 0 = rank-deficient sketch met, bit 1 = non-finite S.  a_scale as rsvd's:
+        A = a_scale * stored A, S scales by |a_scale| and V takes its sign."""
+        torch = _torch()
+        if A.dim() != 3:
+            raise ValueError("expected a (B, m, n) tensor")
+        B, m, n = A.shape
+        if not (A.stride(1) == 1 and A.stride(2) >= max(1, m)):
+            A = A.transpose(1, 2).contiguous().transpose(1, 2)
+        odt = self.out_dtype(A.dtype)
+        if out is None:
+            U = torch.empty((B, l, m), dtype=odt, device=A.device).transpose(1, 2)
+            S = torch.empty((B, l), dtype=odt, device=A.device)
+            V = torch.empty((B, l, n), dtype=odt, device=A.device).transpose(1, 2)
+        else:
+            U, S, V = out
+            for X, rows in ((U, m), (V, n)):
+                if tuple(X.shape) != (B, rows, l) or X.dtype != odt or X.stride(1) != 1 or X.stride(2) < rows:
+                    raise ValueError("out: U and V must be (B, rows, l), each matrix column-major, of the result dtype")
+            if tuple(S.shape) != (B, l) or S.dtype != odt or (l > 1 and S.stride(1) != 1):
+                raise ValueError("out: S must be (B, l) with unit stride along l, of the result dtype")
+        d = Desc(m=m, n=n, lda=max(A.stride(2), m), l=l, q=q, dtype=self.abi_dtype(A.dtype), method=int(method),
+                 qr_mode=int(QRMode.Auto), flags=0, seed=seed, a_scale=a_scale)
+        one = B == 1  # a stride of a one-element dimension carries no meaning
+        bd = _capi.BatchDesc(count0=B, count1=1, a_stride0=0 if one else A.stride(0), a_stride1=0, omega_stride=0,
+                             u_stride=U.stride(2) * l if one else U.stride(0), s_stride=l if one else S.stride(0),
+                             v_stride=V.stride(2) * l if one else V.stride(0))
+        info = self._run_batched(d, bd, A, omega, U, S, V, U.stride(2), V.stride(2), return_info, check_errors)
+        return (U, S, V, info) if return_info else (U, S, V)
+
+    def rsvd_tiles(self, A, tile_m: int, tile_n: int, l: int, q: int = 2, method: int = SVDMethod.Jacobi,
+                   omega=None, seed: int = 0, return_info: bool = False, check_errors: bool = True):
+        """One rSVD per tile_m x tile_n tile of the 2-D column-major A (any lda, any storage offset),
+        read in place through strides: the block decomposition of the reference's
+        Image::compress_parallel (image_compression/src/image_com.cpp:350-371).  Returns
+        U (gr, gc, tile_m, l), S (gr, gc, l), V (gr, gc, tile_n, l); tile (i, j) is
+        A[i*tile_m:(i+1)*tile_m, j*tile_n:(j+1)*tile_n] and draws seed + i + gr*j.
+        omega: (tile_n, l) shared, or (gr*gc, tile_n, l) indexed by b = i + gr*j."""
+        torch = _torch()
+        if A.dim() != 2:
+            raise ValueError("expected a matrix")
+        m, n = A.shape
+        if tile_m <= 0 or tile_n <= 0 or m % tile_m or n % tile_n:
+            raise ValueError(f"tile {tile_m} x {tile_n} does not divide the {m} x {n} matrix")
+        A, lda = colmajor(A)
+        gr, gc = m // tile_m, n // tile_n
+        odt = self.out_dtype(A.dtype)
+        Ub = torch.empty((gc, gr, l, tile_m), dtype=odt, device=A.device)
+        Sb = torch.empty((gc, gr, l), dtype=odt, device=A.device)
+        Vb = torch.empty((gc, gr, l, tile_n), dtype=odt, device=A.device)
+        d = Desc(m=tile_m, n=tile_n, lda=max(lda, m), l=l, q=q, dtype=self.abi_dtype(A.dtype), method=int(method),
+                 qr_mode=int(QRMode.Auto), flags=0, seed=seed, a_scale=1.0)
+        bd = _capi.BatchDesc(count0=gr, count1=gc, a_stride0=tile_m, a_stride1=tile_n * max(lda, m), omega_stride=0,
+                             u_stride=tile_m * l, s_stride=l, v_stride=tile_n * l)
+        info = self._run_batched(d, bd, A, omega, Ub, Sb, Vb, tile_m, tile_n, return_info, check_errors)
+        U, S, V = Ub.permute(1, 0, 3, 2), Sb.permute(1, 0, 2), Vb.permute(1, 0, 3, 2)
+        if return_info:
+            return U, S, V, info.view(gc, gr, 2).permute(1, 0, 2)
+        return U, S, V
+
     def range_finder(self, A, omega, q: int = 2, qr_mode: int = QRMode.Auto, out=None):
         """Device intermediate_step: the orthonormal range basis Q (m x l).  out: a column-major
         m x l tensor to write Q into (any leading dimension >= m), as rsvd's out=."""
