@@ -27,6 +27,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "rsvd_c.h"
 
@@ -180,6 +181,23 @@ Mat generate_omega(int n, int l) {
     Context& c = Context::instance();
     check(rsvd_generate_omega_host_f64(c.handle(), n, l, c.next_seed(), Om.data()), "generateOmega");
     return Om;
+}
+
+// Rank-k compression, the numeric core of Image::compress_parallel (image_compression/src/image_com.cpp:
+// 325-404): every tile_m x tile_n tile of A (0, 0: the whole matrix) is replaced in C by
+// U_k diag(S_k) V_k^T of its rSVD of width l (k = l is what the reference rebuilds).  err2 (optional):
+// per tile (i, j), at 2 (i + (m / tile_m) j), ||A_tile||_F^2 and ||A_tile - C_tile||_F^2.  C may be A.
+template <class Mat>
+void compress(const Mat& A, Mat& C, int l, int k, int tile_m = 0, int tile_n = 0, int q = 2,
+              std::vector<double>* err2 = nullptr) {
+    const int64_t m = A.rows(), n = A.cols();
+    if (&C != &A) C.resize(m, n);
+    const int64_t tm = tile_m ? tile_m : m, tn = tile_n ? tile_n : n;
+    if (err2) err2->assign(tm > 0 && tn > 0 ? 2 * (m / tm) * (n / tn) : 0, 0.0);
+    Context& c = Context::instance();
+    check(rsvd_compress_host_f64(c.handle(), m, n, A.data(), m, tile_m, tile_n, l, k, q, c.next_seed(), C.data(), m,
+                                 err2 ? err2->data() : nullptr),
+          "compress");
 }
 
 // qr_decomposition_reduced(A, Q, R) (src/QR.cpp:43-80): Q m x n, R n x n; requires m >= n.

@@ -16,6 +16,11 @@
  *                                          Mat_m& R)              include/QR.hpp:15-16, src/QR.cpp:22-80
  *   rsvd_svd                       <- template<SVDMethod> SVD::compute()/getU/getS/getV
  *                                                                  include/SVD_class.hpp:35-71,79-180
+ *   rsvd_run_batched               <- one rSVD per block, Image::compress_parallel
+ *                                                                  image_compression/src/image_com.cpp:350-371
+ *   rsvd_compress_batched /        <- localMatrix = U * S.asDiagonal() * V.transpose() put back into the
+ *   rsvd_lowrank /                    image (image_com.cpp:374, :381-394; Image::reconstruct :184-190) and
+ *   rsvd_compress_host_f64            ||A - U diag(S) V^T||_F (tests/rSVD_test.cpp:77-95)
  * The C++ drop-in headers include/rSVD.hpp, include/QR.hpp, include/SVD_class.hpp sit on top of
  * these symbols with the reference's exact signatures.
  *
@@ -33,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RSVD_ABI_VERSION 7
+#define RSVD_ABI_VERSION 8
 
 typedef enum {
     RSVD_OK = 0,
@@ -286,6 +291,68 @@ int rsvd_batched_workspace_bytes(const rsvd_desc_t *desc, const rsvd_batch_t *ba
 /* Host-only: 1 when the description takes the fused kernel, 0 when it loops (or is invalid). */
 int rsvd_batched_is_fused(const rsvd_desc_t *desc, const rsvd_batch_t *batch);
 
+/* ---- rank-k compression (ABI 8): the rebuild and its error, fused into the batched rSVD ------ */
+
+/* What every caller of the reference's rSVD does next: rebuild the low-rank matrix,
+ * localMatrix = U * S.asDiagonal() * V.transpose() (image_compression/src/image_com.cpp:374,
+ * Image::reconstruct :184-190), put each block back into the image (:381-394), and measure
+ * ||A - U diag(S) V^T||_F (tests/rSVD_test.cpp:77-95).
+ *   C_b   = U_b[:, :k] diag(S_b[:k]) V_b[:, :k]^T, 1 <= k <= min(l, n) (k = l is what the reference
+ *           rebuilds), column-major with its own ldc, in the result dtype (fp64 for fp64 A, fp32 for
+ *           every other A).  S carries |a_scale| and V its sign, so C approximates a_scale * A.
+ *   err2  = two fp64 words per matrix, on the device: err2[2b] = ||a_scale A_b||_F^2 and
+ *           err2[2b + 1] = ||a_scale A_b - C_b||_F^2 with C_b as stored (after rounding to its type).
+ *           Both are fp64 sums in a fixed order (per thread, a 64-lane butterfly, waves and workgroups
+ *           in index order; no atomics): bit-reproducible, independent of the grid, of the position
+ *           in the batch and of the workspace's contents.
+ * C_b = C + i0 * c_stride0 + i1 * c_stride1 (elements), as A_b in rsvd_batch_t.  The C blocks of a batch
+ * must be pairwise disjoint; two layouts are accepted (a stride of a count of 1 is not looked at):
+ *   tile grid      c_stride0 >= m, (count0 - 1) * c_stride0 + m <= ldc, c_stride1 >= n * ldc
+ *   strided batch  c_stride0 >= (n - 1) * ldc + m and (count1 == 1 or c_stride1 >= count0 * c_stride0)
+ * In place: C may be A itself -- same pointer, ldc == lda, the strides of A, A already of C's type (F64 /
+ * F32); A's strides then fall under the same rule (overlapping tiles cannot be compressed in place).
+ * Every element of A is read for the error and overwritten by the same thread, after the last
+ * projection has finished with the tile.  Any other overlap of C with A is the caller's error. */
+typedef struct {
+    int32_t k, reserved;
+    int64_t ldc, c_stride0, c_stride1;
+} rsvd_compress_t;
+
+/* rsvd_run_batched followed by the rebuild and the error of every matrix.  C nullable when err2 is set
+ * (error only); U, S, V all NULL or all set; err2 nullable; info as rsvd_run_batched's.  The fused path is
+ * taken exactly when rsvd_batched_is_fused(desc, batch) == 1 and is still ONE launch: the rebuild runs in
+ * the workgroup that holds the matrix's factors in LDS, and with U = S = V = NULL the factors never reach
+ * global memory.  U, S, V and info, where asked for, are bit-identical to rsvd_run_batched's.  Outside
+ * the fused limits entry b is rsvd_run with seed + b followed by rsvd_lowrank, bit for bit, on the
+ * handle's stream (factors the caller did not ask for live in the workspace).
+ * RSVD_ERR_INVALID_ARG: what rsvd_run_batched refuses, k outside 1 .. min(l, n), ldc < m, a negative or
+ * overlapping C stride, a partial set of U, S, V, C == A with another ldc / strides / a low-precision A.
+ * RSVD_ERR_UNSUPPORTED: as rsvd_run_batched. */
+int rsvd_compress_batched(rsvd_handle_t h, const rsvd_desc_t *desc, const rsvd_batch_t *batch,
+                          const rsvd_compress_t *comp, const void *A, const void *omega, int64_t ldo,
+                          void *C /* nullable if err2 */, void *U, int64_t ldu, void *S, void *V,
+                          int64_t ldv /* U, S, V: all NULL or all set */,
+                          double *err2 /* nullable, device, 2 per matrix */,
+                          int32_t *info /* nullable, device, 2 per matrix */);
+/* Host-only.  Device workspace bytes of rsvd_compress_batched (batch->u_stride / s_stride / v_stride are
+ * not looked at).  Fused: exactly rsvd_batched_workspace_bytes (the tail needs no memory of its own);
+ * looped: one rsvd_run, the error slots of rsvd_lowrank and one matrix's factors. */
+int rsvd_compress_workspace_bytes(const rsvd_desc_t *desc, const rsvd_batch_t *batch, const rsvd_compress_t *comp,
+                                  size_t *bytes);
+
+/* C (m x n, ldc) = U[:, :k] diag(S[:k]) V[:, :k]^T for any m, n and k <= 4096 (MFMA, 64 x 64 tiles).
+ * dtype F64 / F32 is the type of U (ldu >= m), S, V (ldv >= n) and C.  With A (m x n, lda, a_dtype F64 for
+ * dtype F64, else F32 / BF16 / FP8_E4M3; the matrix is a_scale * A, a_scale 0 means 1) and err2 (device,
+ * 2 fp64 words as above) the error is computed in the same pass.  C nullable when A and err2 are set
+ * (error only, same words bit for bit); A nullable (no error; err2 must then be NULL).  C may be A
+ * itself when A has C's type (each element is read and overwritten by one thread); U, S, V may not
+ * overlap C.  Asynchronous on the handle's stream. */
+int rsvd_lowrank(rsvd_handle_t h, int64_t m, int64_t n, int32_t k, int32_t dtype, const void *U, int64_t ldu,
+                 const void *S, const void *V, int64_t ldv, void *C, int64_t ldc, const void *A, int64_t lda,
+                 int32_t a_dtype, double a_scale, double *err2);
+/* Host-only.  Device workspace bytes of rsvd_lowrank with an error (2 fp64 words per 64 x 64 tile of C). */
+int rsvd_lowrank_workspace_bytes(int64_t m, int64_t n, size_t *bytes);
+
 /* ---- host-pointer fp64 entry points used by the C++ drop-in headers (synchronous) --------- */
 int rsvd_run_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, int64_t lda, int32_t l,
                       int32_t q, int32_t method, const double *omega /* nullable, n x l, ld n */,
@@ -300,6 +367,14 @@ int rsvd_qr_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, int
 /* U: m x min(m,n), S: min(m,n), V: n x min(m,n) buffers (ld m, n); *kept columns are written. */
 int rsvd_svd_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, int64_t lda, int32_t method, int32_t r,
                       uint64_t seed, double *U, double *S, double *V, int32_t *kept);
+/* Image::compress_parallel's numeric core on host buffers: every tile_m x tile_n tile of A (tile_m =
+ * tile_n = 0: the whole matrix as one tile; the tiles must divide it) is replaced by its rank-k rebuild
+ * from an rSVD of width l with q power iterations, Omega = Philox(seed + i + (m / tile_m) * j) for tile
+ * (i, j).  C: m x n, ldc (may be A).  err2 (host, nullable): the two words of rsvd_compress_batched per
+ * tile, tile (i, j) at 2 * (i + (m / tile_m) * j). */
+int rsvd_compress_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, int64_t lda, int32_t tile_m,
+                           int32_t tile_n, int32_t l, int32_t k, int32_t q, uint64_t seed, double *C, int64_t ldc,
+                           double *err2 /* host, 2 per tile, nullable */);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     SVD,
     SVDMethod,
     colmajor,
+    compression_ratio,
     default_engine,
     empty_colmajor,
     generateOmega,
@@ -25,6 +26,7 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "build", "row_partition", "RSVDError", "Engine", "QRMode", "SVDMethod", "colmajor",
+    "compression_ratio",
     "default_engine", "empty_colmajor", "generateOmega", "intermediate_step", "make_allreduce_hook",
     "make_collective_hook", "rSVD",
     "rSVD_image_compression",

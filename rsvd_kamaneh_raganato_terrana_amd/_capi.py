@@ -43,6 +43,8 @@ EXPORTS = (
     "rsvd_svd_workspace_bytes", "rsvd_qr_host_f64", "rsvd_svd_host_f64",
     "rsvd_comm_unique_id", "rsvd_comm_init", "rsvd_comm_destroy",
     "rsvd_run_batched", "rsvd_batched_workspace_bytes", "rsvd_batched_is_fused",
+    "rsvd_compress_batched", "rsvd_compress_workspace_bytes", "rsvd_lowrank", "rsvd_lowrank_workspace_bytes",
+    "rsvd_compress_host_f64",
 )
 
 
@@ -80,6 +82,14 @@ class BatchDesc(ctypes.Structure):
     ]
 
 
+class CompressDesc(ctypes.Structure):
+    """rsvd_compress_t (include/rsvd_c.h, ABI 8): the rank and where the rebuilt blocks go."""
+    _fields_ = [
+        ("k", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("ldc", ctypes.c_int64), ("c_stride0", ctypes.c_int64), ("c_stride1", ctypes.c_int64),
+    ]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                 ctypes.c_void_p, ctypes.c_void_p)
 # rsvd_collective_fn(op, send, recv, count, dtype, stream, user) -- ABI 5
@@ -91,9 +101,9 @@ COLL_REDUCE_SCATTER, COLL_ALL_GATHER = 1, 2
 def _sources():
     """The files librsvd_hip.so is built from, in the order the Makefile hashes them."""
     hip = ("util.hip proj.hip qr.hip jacobi.hip wide_proj.hip wide_gram.hip wide_chol.hip wide_panel.hip wide_svd.hip "
-           "wide_eig.hip dense.hip gemm.hip batched.hip").split()
+           "wide_eig.hip dense.hip gemm.hip batched.hip lowrank.hip").split()
     cpp = "driver.cpp wide.cpp wide_plan.cpp dense_api.cpp comm.cpp dense_big.cpp batched_run.cpp".split()
-    hdr = "common.hpp kernels.hpp wide.hpp wide_dev.hpp dense.hpp handle.hpp batched.hpp".split()
+    hdr = "common.hpp kernels.hpp wide.hpp wide_dev.hpp dense.hpp handle.hpp batched.hpp lowrank.hpp".split()
     return ([os.path.join(CSRC, f) for f in hip + cpp + hdr] + [os.path.join(REPO, "include", "rsvd_c.h")]
             + [os.path.join(CSRC, "Makefile")])
 
@@ -185,6 +195,12 @@ def lib():
     L.rsvd_run_batched.argtypes = [vp, ctypes.POINTER(Desc), bp, vp, vp, i64, vp, i64, vp, vp, i64, vp]
     L.rsvd_batched_workspace_bytes.argtypes = [ctypes.POINTER(Desc), bp, szp]
     L.rsvd_batched_is_fused.argtypes = [ctypes.POINTER(Desc), bp]
+    cp = ctypes.POINTER(CompressDesc)
+    L.rsvd_compress_batched.argtypes = [vp, ctypes.POINTER(Desc), bp, cp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]
+    L.rsvd_compress_workspace_bytes.argtypes = [ctypes.POINTER(Desc), bp, cp, szp]
+    L.rsvd_lowrank.argtypes = [vp, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, ctypes.c_double, vp]
+    L.rsvd_lowrank_workspace_bytes.argtypes = [i64, i64, szp]
+    L.rsvd_compress_host_f64.argtypes = [vp, i64, i64, dp, i64, i32, i32, i32, i32, i32, u64, dp, i64, dp]
     _LIB = L
     return L
 

@@ -460,6 +460,204 @@ class Engine:
             return U, S, V, info.view(gc, gr, 2).permute(1, 0, 2)
         return U, S, V
 
+    # -- rank-k compression (rsvd_compress_batched / rsvd_lowrank, include/rsvd_c.h ABI 8) ---------
+    @staticmethod
+    def _check_k(k, l: int, n: int) -> int:
+        k = l if k is None else int(k)
+        if not 1 <= k <= min(l, n):
+            raise ValueError(f"k = {k} must be in 1 .. min(l, n) = {min(l, n)}")
+        return k
+
+    def _run_compress(self, d: Desc, bd, cd, A, omega, C, factors, return_err: bool, return_info: bool,
+                      check_errors: bool):
+        """Reserve, bind the stream and enqueue one rsvd_compress_batched (omega as _run_batched's)."""
+        torch = _torch()
+        odt = self.out_dtype(A.dtype)
+        batch = bd.count0 * bd.count1
+        om_ptr, ldo = 0, 0
+        if omega is not None:
+            om = omega.to(device=A.device, dtype=odt)
+            if om.dim() == 2:
+                om, ldo = colmajor(om)
+                bd.omega_stride = 0
+            elif om.dim() == 3 and om.shape[0] == batch:
+                if not (om.stride(1) == 1 and om.stride(2) >= max(1, om.shape[1])):
+                    om = om.transpose(1, 2).contiguous().transpose(1, 2)
+                ldo = om.stride(2)
+                bd.omega_stride = om.stride(0) if batch > 1 else 0
+            else:
+                raise ValueError("omega must be (n, l) or (batch, n, l)")
+            if tuple(om.shape[-2:]) != (d.n, d.l):
+                raise ValueError("omega must have n rows and l columns")
+            om_ptr = om.data_ptr()
+        nbytes = ctypes.c_size_t(0)
+        check(lib().rsvd_compress_workspace_bytes(ctypes.byref(d), ctypes.byref(bd), ctypes.byref(cd),
+                                                  ctypes.byref(nbytes)))
+        self._reserve_bytes(nbytes.value)
+        self._bind_stream()
+        err = torch.zeros((batch, 2), dtype=torch.float64, device=A.device) if return_err else None
+        info = torch.zeros((batch, 2), dtype=torch.int32, device=A.device) if return_info else None
+        U, S, V, ldu, ldv = factors if factors is not None else (None, None, None, 0, 0)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        check(lib().rsvd_compress_batched(self.h, ctypes.byref(d), ctypes.byref(bd), ctypes.byref(cd), ptr(A),
+                                          ctypes.c_void_p(om_ptr), ldo, ptr(C), ptr(U), ldu, ptr(S), ptr(V), ldv,
+                                          ptr(err), ptr(info)), self.h)
+        if check_errors:
+            self.sync()
+        return err, info
+
+    def compress_batched(self, A, l: int, k=None, q: int = 2, omega=None, seed: int = 0, out=None,
+                         in_place: bool = False, return_factors: bool = False, return_err: bool = True,
+                         return_info: bool = False, check_errors: bool = True, a_scale: float = 1.0):
+        """Rank-k compression of every matrix of a CUDA tensor A (B, m, n): C (B, m, n), each matrix
+        column-major, C[b] = U[:, :k] diag(S[:k]) V[:, :k]^T of rsvd_batched's entry b (k = l when None;
+        what Image::compress_parallel rebuilds, image_compression/src/image_com.cpp:374), in
+        out_dtype(A.dtype).  err (B, 2) float64 on the device: ||a_scale A[b]||_F^2 and
+        ||a_scale A[b] - C[b]||_F^2 with C as stored.  Inside the fused limits (batched_is_fused) the
+        rebuild and the error run in the same ONE launch as the rSVD and, without return_factors, the
+        factors never leave the workgroup.  in_place: C overwrites A (fp64 / fp32 A, every matrix
+        column-major and not overlapping its neighbours) and A itself is returned.
+        Returns C, then err if return_err, then (U, S, V) if return_factors, then info if return_info."""
+        torch = _torch()
+        if A.dim() != 3:
+            raise ValueError("expected a (B, m, n) tensor")
+        B, m, n = A.shape
+        k = self._check_k(k, l, n)
+        odt = self.out_dtype(A.dtype)
+        colm = A.stride(1) == 1 and A.stride(2) >= max(1, m)
+        if in_place:
+            if A.dtype != odt:
+                raise ValueError("in_place needs an A of the result dtype (float64 or float32)")
+            if not colm:
+                raise ValueError("in_place needs every A[b] column-major")
+            if out is not None:
+                raise ValueError("in_place and out= exclude each other")
+            C = A
+        else:
+            if not colm:
+                A = A.transpose(1, 2).contiguous().transpose(1, 2)
+            C = torch.empty((B, n, m), dtype=odt, device=A.device).transpose(1, 2) if out is None else out
+            if tuple(C.shape) != (B, m, n) or C.dtype != odt or C.stride(1) != 1 or C.stride(2) < m:
+                raise ValueError("out: C must be (B, m, n), each matrix column-major, of the result dtype")
+        factors = None
+        if return_factors:
+            U = torch.empty((B, l, m), dtype=odt, device=A.device).transpose(1, 2)
+            S = torch.empty((B, l), dtype=odt, device=A.device)
+            V = torch.empty((B, l, n), dtype=odt, device=A.device).transpose(1, 2)
+            factors = (U, S, V, m, n)
+        d = Desc(m=m, n=n, lda=max(A.stride(2), m), l=l, q=q, dtype=self.abi_dtype(A.dtype),
+                 method=int(SVDMethod.Jacobi), qr_mode=int(QRMode.Auto), flags=0, seed=seed, a_scale=a_scale)
+        one = B == 1  # a stride of a one-element dimension carries no meaning
+        bd = _capi.BatchDesc(count0=B, count1=1, a_stride0=0 if one else A.stride(0), a_stride1=0, omega_stride=0,
+                             u_stride=m * l, s_stride=l, v_stride=n * l)
+        cd = _capi.CompressDesc(k=k, reserved=0, ldc=max(C.stride(2), m), c_stride0=0 if one else C.stride(0),
+                                c_stride1=0)
+        err, info = self._run_compress(d, bd, cd, A, omega, C, factors, return_err, return_info, check_errors)
+        res = [C] + ([err] if return_err else []) + ([factors[:3]] if return_factors else [])
+        res += [info] if return_info else []
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def compress_tiles(self, A, tile_m: int, tile_n: int, l: int, k=None, q: int = 2, omega=None, seed: int = 0,
+                       out=None, in_place: bool = False, return_factors: bool = False, return_err: bool = True,
+                       return_info: bool = False, check_errors: bool = True, a_scale: float = 1.0):
+        """Image::compress_parallel's numeric core (image_compression/src/image_com.cpp:325-404): every
+        tile_m x tile_n tile of the 2-D column-major A is replaced by its rank-k rebuild, in one launch
+        inside the fused limits.  Returns C (m, n) column-major -- A itself when in_place -- and
+        err (gr, gc, 2) as compress_batched's; tile (i, j) draws seed + i + gr*j, exactly as rsvd_tiles;
+        factors come back in rsvd_tiles' shapes, info as (gr, gc, 2)."""
+        torch = _torch()
+        if A.dim() != 2:
+            raise ValueError("expected a matrix")
+        m, n = A.shape
+        if tile_m <= 0 or tile_n <= 0 or m % tile_m or n % tile_n:
+            raise ValueError(f"tile {tile_m} x {tile_n} does not divide the {m} x {n} matrix")
+        k = self._check_k(k, l, tile_n)
+        odt = self.out_dtype(A.dtype)
+        if in_place:
+            if A.dtype != odt:
+                raise ValueError("in_place needs an A of the result dtype (float64 or float32)")
+            if not (A.stride(0) == 1 and A.stride(1) >= max(1, m)):
+                raise ValueError("in_place needs a column-major A")
+            if out is not None:
+                raise ValueError("in_place and out= exclude each other")
+            lda = A.stride(1)
+            C = A
+        else:
+            A, lda = colmajor(A)
+            C = empty_colmajor(m, n, odt, A.device) if out is None else out
+            if tuple(C.shape) != (m, n) or C.dtype != odt or C.stride(0) != 1 or C.stride(1) < m:
+                raise ValueError("out: C must be (m, n), column-major, of the result dtype")
+        gr, gc = m // tile_m, n // tile_n
+        factors = None
+        if return_factors:
+            Ub = torch.empty((gc, gr, l, tile_m), dtype=odt, device=A.device)
+            Sb = torch.empty((gc, gr, l), dtype=odt, device=A.device)
+            Vb = torch.empty((gc, gr, l, tile_n), dtype=odt, device=A.device)
+            factors = (Ub, Sb, Vb, tile_m, tile_n)
+        lda, ldc = max(lda, m), max(C.stride(1), m)
+        d = Desc(m=tile_m, n=tile_n, lda=lda, l=l, q=q, dtype=self.abi_dtype(A.dtype), method=int(SVDMethod.Jacobi),
+                 qr_mode=int(QRMode.Auto), flags=0, seed=seed, a_scale=a_scale)
+        bd = _capi.BatchDesc(count0=gr, count1=gc, a_stride0=tile_m, a_stride1=tile_n * lda, omega_stride=0,
+                             u_stride=tile_m * l, s_stride=l, v_stride=tile_n * l)
+        cd = _capi.CompressDesc(k=k, reserved=0, ldc=ldc, c_stride0=tile_m, c_stride1=tile_n * ldc)
+        err, info = self._run_compress(d, bd, cd, A, omega, C, factors, return_err, return_info, check_errors)
+        res = [C] + ([err.view(gc, gr, 2).permute(1, 0, 2)] if return_err else [])
+        if return_factors:
+            res.append((factors[0].permute(1, 0, 3, 2), factors[1].permute(1, 0, 2), factors[2].permute(1, 0, 3, 2)))
+        res += [info.view(gc, gr, 2).permute(1, 0, 2)] if return_info else []
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def lowrank(self, U, S, V, k=None, A=None, out=None, a_scale: float = 1.0):
+        """C = U[:, :k] diag(S[:k]) V[:, :k]^T (Image::reconstruct, image_compression/src/image_com.cpp:
+        184-190) for factors of any size, column-major in their dtype (float64 / float32); k = all of
+        them when None.  With A (m x n: float64 for float64 factors, else float32 / bfloat16 /
+        float8_e4m3fn; the matrix is a_scale * A) also returns err (2,) float64 on the device:
+        ||a_scale A||_F^2 and ||a_scale A - C||_F^2, computed in the same pass.  out: a column-major
+        (m, n) tensor to write into (A itself compresses in place); out=False with A: the error alone."""
+        torch = _torch()
+        if U.dim() != 2 or V.dim() != 2 or S.dim() != 1:
+            raise ValueError("expected U (m, d), S (d), V (n, d)")
+        m, n, dd = U.shape[0], V.shape[0], S.shape[0]
+        if U.shape[1] != dd or V.shape[1] != dd or U.dtype != S.dtype or V.dtype != S.dtype:
+            raise ValueError("U, S and V must share their dtype and their number of columns")
+        if U.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"unsupported dtype {U.dtype}")
+        k = dd if k is None else int(k)
+        if not 1 <= k <= dd:
+            raise ValueError(f"k = {k} must be in 1 .. {dd}")
+        if A is not None and (tuple(A.shape) != (m, n) or self.out_dtype(A.dtype) != U.dtype):
+            raise ValueError("A must be (m, n) with the factors as its result dtype")
+        if out is False and A is None:
+            raise ValueError("nothing to compute: no C and no A")
+        U, ldu = colmajor(U)
+        V, ldv = colmajor(V)
+        S = S.contiguous()
+        if out is None:
+            C = empty_colmajor(m, n, U.dtype, U.device)
+        elif out is False:
+            C = None
+        else:
+            C = out
+            if tuple(C.shape) != (m, n) or C.dtype != U.dtype or C.stride(0) != 1 or C.stride(1) < m:
+                raise ValueError("out: C must be (m, n), column-major, of the factors' dtype")
+        lda, a_dt, err = 0, 0, None
+        if A is not None:
+            if not (C is not None and A.data_ptr() == C.data_ptr()):
+                A, _ = colmajor(A)
+            lda, a_dt = max(A.stride(1), m), self.abi_dtype(A.dtype)
+            err = torch.zeros(2, dtype=torch.float64, device=U.device)
+            nbytes = ctypes.c_size_t(0)
+            check(lib().rsvd_lowrank_workspace_bytes(m, n, ctypes.byref(nbytes)))
+            self._reserve_bytes(nbytes.value)
+        self._bind_stream()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        check(lib().rsvd_lowrank(self.h, m, n, k, self.abi_dtype(U.dtype), ptr(U), max(ldu, m), ptr(S), ptr(V),
+                                 max(ldv, n), ptr(C), max(C.stride(1), m) if C is not None else 0, ptr(A), lda, a_dt,
+                                 a_scale, ptr(err)), self.h)
+        if A is None:
+            return C
+        return err if C is None else (C, err)
+
     def range_finder(self, A, omega, q: int = 2, qr_mode: int = QRMode.Auto, out=None):
         """Device intermediate_step: the orthonormal range basis Q (m x l).  out: a column-major
         m x l tensor to write Q into (any leading dimension >= m), as rsvd's out=."""
@@ -620,6 +818,12 @@ class Engine:
 
 
 _DEFAULT: Optional[Engine] = None
+
+
+def compression_ratio(m: int, n: int, l: int) -> float:
+    """Image::get_compression_ratio (image_compression/src/image_com.cpp:406-410): the m x n matrix
+    against its l triplets, m n / (l (m + n + 1))."""
+    return m * n / (l * (m + n + 1))
 
 
 def default_engine() -> Engine:

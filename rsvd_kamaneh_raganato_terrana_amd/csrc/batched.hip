@@ -9,6 +9,9 @@
 //   Pn = B^T = A^T Pm ; B^T = Q_B R (R kept, Pn = Q_B)                   B = Q^T A         src/rSVD.cpp:89
 //   W = R^T = U_w S V_w^T, one-sided Jacobi in LDS (as jacobi.hip)       SVD<Jacobi>       SVD_class.hpp:126-178
 //   U = Pm U_w ; V = Pn V_w                                              U = Q * Utilde    src/rSVD.cpp:128
+// and, for a compress call (COMP), from the same LDS contents:
+//   C = U_k diag(S_k) V_k^T over or beside A, ||A||_F^2, ||A - C||_F^2   localMatrix = U * S.asDiagonal() *
+//                                             V.transpose()  image_compression/src/image_com.cpp:374, :381-394
 //
 // Pm (m x l) and Pn (n x l) are column-major panels in T, in LDS behind the l x l area when they fit
 // in the 160 KiB budget, else in the workgroup's slice of the handle workspace.  A is read in place
@@ -459,7 +462,116 @@ __device__ __forceinline__ void build_uw(char* sm, int l) {
     }
 }
 
-template <typename T, int LP, bool PLDS>
+// ---- the compress tail: C = U_k diag(S_k) V_k^T and its error, from what is still in LDS ---------
+//
+// P (rows x l, column-major ld rows) becomes, in place, the rows x k factor
+//   F[i, r] = scale(r) * sum_t P[i, t] W[t, src(r)],   src(r) = inv ? inv[r] : r,
+//   scale(r) = sig ? sig[src(r)] : 1.
+// A row of F depends on the same row of P alone, so a round takes whole rows: every thread of the
+// round reads its row into 8 accumulators, one barrier, then the row is overwritten.  Rounds touch
+// disjoint rows and need no barrier between them.  W has LP >= 8 ceil(k / 8) columns and inv as many
+// entries, so the columns past k of the last chunk are summed unclamped and dropped.  tid: the thread
+// index through a value the compiler cannot see through, so that nothing derived from it is hoisted
+// out of the kernel's loop over matrices into registers the projections need.
+template <typename T, typename TW>
+__device__ void scale_panel(int tid, T* P, int rows, int l, int k, const TW* W, int ldw, const int* inv,
+                            const double* sig) {
+    const int nch = (k + 7) / 8;
+    const int R = blockDim.x / nch;  // rows of a round
+    const int ch = tid / R, ri = tid % R;
+    for (int r0 = 0; r0 < rows; r0 += R) {
+        const int i = r0 + ri;
+        const bool on = ch < nch && i < rows;
+        double acc[8];
+        int cc[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            acc[c] = 0.0;
+            cc[c] = (inv ? inv[ch * 8 + c] : ch * 8 + c) * ldw;
+        }
+        if (on)
+            for (int t = 0; t < l; ++t) {
+                const double pv = (double)P[i + t * rows];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) acc[c] = fma(pv, (double)W[t + cc[c]], acc[c]);
+            }
+        __syncthreads();
+        if (on) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (ch * 8 + c < k) {
+                    const int r = ch * 8 + c;
+                    P[i + r * rows] = (T)(sig ? acc[c] * sig[inv ? inv[r] : r] : acc[c]);
+                }
+        }
+    }
+    __syncthreads();
+}
+
+// C (m x n, ldc; nullable) = asc Fm Fn^T with the projections' item shape (one row, 8 columns, the k sum
+// in order, fp64 accumulators, scaled by asc = a_scale and rounded to T once: C of a scaled call is the
+// unscaled C times a_scale to one rounding).  The item that owns C[i, j] also reads A[i, j] -- before it
+// stores, so C may be A itself -- and adds (asc a)^2 and (asc a - c)^2 to its two fp64 sums.  Those
+// are joined in a fixed order: per thread over its items, the 64-lane butterfly, the waves in index
+// order.  part: 2 x waves fp64 words of scratch.
+template <typename T>
+__device__ void rebuild_tile(int tid, const T* Fm, int m, const T* Fn, int n, int k, const T* A, int64_t lda,
+                             double asc, T* C, int64_t ldc, double* part, double* err2) {
+#pragma clang fp contract(off)  // a - c is taken from C as stored, not from the unrounded product
+    const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const int nch = (n + 7) / 8;
+    double sa = 0.0, se = 0.0;
+    for (int it = tid; it < m * nch; it += blockDim.x) {
+        const int i = it % m, j0 = (it / m) * 8;
+        double acc[8];
+        int cc[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            acc[c] = 0.0;
+            cc[c] = j0 + c < n ? j0 + c : n - 1;
+        }
+        for (int r = 0; r < k; ++r) {
+            const double f = (double)Fm[i + r * m];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[c] = fma(f, (double)Fn[cc[c] + r * n], acc[c]);
+        }
+        const T* ap = A + i + (int64_t)j0 * lda;  // one column at a time: the two sums are a chain anyway
+        T* cp = C ? C + i + (int64_t)j0 * ldc : nullptr;
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            if (j0 + c < n) {
+                const T cv = (T)(acc[c] * asc);
+                const double av = (double)*ap * asc;
+                const double d = av - (double)cv;
+                sa = fma(av, av, sa);
+                se = fma(d, d, se);
+                if (cp) {
+                    *cp = cv;
+                    cp += ldc;
+                }
+                ap += lda;
+            }
+    }
+    sa = warp_sum(sa);
+    se = warp_sum(se);
+    if (lane == 0) {
+        part[2 * wave] = sa;
+        part[2 * wave + 1] = se;
+    }
+    __syncthreads();
+    if (tid == 0 && err2) {
+        double ta = 0.0, te = 0.0;
+        for (int w = 0; w < nw; ++w) {
+            ta += part[2 * w];
+            te += part[2 * w + 1];
+        }
+        err2[0] = ta;
+        err2[1] = te;
+    }
+    __syncthreads();
+}
+
+template <typename T, int LP, bool PLDS, bool COMP>
 __global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(BatchedArgs a) {
     typedef BShape<T, LP> SH;
     constexpr int CS = SH::CS;
@@ -533,15 +645,32 @@ __global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(Batch
         house_form_q<T>(Pn, n, l, tau);
         const int sweeps = jacobi_lds<T, LP>(bsm, l);
         // V = Q_B V_w (column rank[c] from rotation column c), S, then U = Q U_w
-        gemm_nn<T, T, T>(Pn, n, n, l, J, CS, l, Vb, a.ldv, rank, a.v_neg ? -1.0 : 1.0);
+        const bool factors = !COMP || a.U != nullptr;  // a compress call may keep them out of global memory
+        if (factors) gemm_nn<T, T, T>(Pn, n, n, l, J, CS, l, Vb, a.ldv, rank, a.v_neg ? -1.0 : 1.0);
         for (int c = tid; c < l; c += nt) {
             const T sv = (T)(sig[c] * a.s_scale);
             if (!isfinite(sv)) flags[kFlNonFinite] = 1;
-            Sb[rank[c]] = sv;
+            if (factors) Sb[rank[c]] = sv;
         }
         build_uw<T, LP>(bsm, l);
-        gemm_nn<T, double, T>(Pm, m, m, l, Ud, LP, l, Ub, a.ldu, nullptr, 1.0);
+        if (factors) gemm_nn<T, double, T>(Pm, m, m, l, Ud, LP, l, Ub, a.ldu, nullptr, 1.0);
         __syncthreads();
+        if (COMP) {
+            // Pm <- U_k = Pm U_w[:, :k]; Pn <- Pn V_w[:, column of rank r] * sigma_r; then
+            // C = a_scale Pm Pn^T (|a_scale| is S's, the sign V's) against a_scale A.  tau is free after
+            // the last Q: it holds the inverse of rank[].
+            int* inv = reinterpret_cast<int*>(tau);
+            for (int c = tid; c < LP; c += nt) inv[rank[c]] = c;  // padding columns keep their own index
+            __syncthreads();
+            int ct = tid;
+            asm volatile("" : "+v"(ct));
+            const double asc = a.v_neg ? -a.s_scale : a.s_scale;
+            scale_panel<T, double>(ct, Pm, m, l, a.k, Ud, LP, nullptr, nullptr);
+            scale_panel<T, T>(ct, Pn, n, l, a.k, J, CS, inv, sig);
+            T* Cb = a.C ? reinterpret_cast<T*>(a.C) + i0 * a.c_stride0 + i1 * a.c_stride1 : nullptr;
+            rebuild_tile<T>(ct, Pm, m, Pn, n, a.k, A, a.lda, asc, Cb, a.ldc, scr,
+                            a.err2 ? a.err2 + 2 * b : nullptr);
+        }
         if (tid == 0) {
             const int nf = flags[kFlNonFinite];
             if (nf) atomicOr(a.nonfinite, 1);
@@ -554,23 +683,23 @@ __global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(Batch
     }
 }
 
-template <typename T, int LP>
+template <typename T, int LP, bool COMP>
 hipError_t launch_tl(const BatchedArgs& a, bool plds, size_t lds, int grid, hipStream_t s) {
     typedef BShape<T, LP> SH;
     if (plds)
-        hipLaunchKernelGGL((batched_rsvd_kernel<T, LP, true>), dim3(grid), dim3(SH::NT), lds, s, a);
+        hipLaunchKernelGGL((batched_rsvd_kernel<T, LP, true, COMP>), dim3(grid), dim3(SH::NT), lds, s, a);
     else
-        hipLaunchKernelGGL((batched_rsvd_kernel<T, LP, false>), dim3(grid), dim3(SH::NT), lds, s, a);
+        hipLaunchKernelGGL((batched_rsvd_kernel<T, LP, false, COMP>), dim3(grid), dim3(SH::NT), lds, s, a);
     return hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool COMP>
 hipError_t launch_t(const BatchedArgs& a, int LP, bool plds, size_t lds, int grid, hipStream_t s) {
     switch (LP) {
-        case 16: return launch_tl<T, 16>(a, plds, lds, grid, s);
-        case 32: return launch_tl<T, 32>(a, plds, lds, grid, s);
-        case 48: return launch_tl<T, 48>(a, plds, lds, grid, s);
-        case 64: return launch_tl<T, 64>(a, plds, lds, grid, s);
+        case 16: return launch_tl<T, 16, COMP>(a, plds, lds, grid, s);
+        case 32: return launch_tl<T, 32, COMP>(a, plds, lds, grid, s);
+        case 48: return launch_tl<T, 48, COMP>(a, plds, lds, grid, s);
+        case 64: return launch_tl<T, 64, COMP>(a, plds, lds, grid, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -594,8 +723,14 @@ size_t batched_panel_bytes(int dtype, int m, int n, int l) {
 
 hipError_t launch_batched_rsvd(const BatchedArgs& a, int dtype, int LP, bool panels_in_lds, size_t lds_bytes, int grid,
                                hipStream_t s) {
-    if (dtype == 0) return launch_t<double>(a, LP, panels_in_lds, lds_bytes, grid, s);
-    return launch_t<float>(a, LP, panels_in_lds, lds_bytes, grid, s);
+    if (dtype == 0) return launch_t<double, false>(a, LP, panels_in_lds, lds_bytes, grid, s);
+    return launch_t<float, false>(a, LP, panels_in_lds, lds_bytes, grid, s);
+}
+
+hipError_t launch_batched_compress(const BatchedArgs& a, int dtype, int LP, bool panels_in_lds, size_t lds_bytes,
+                                   int grid, hipStream_t s) {
+    if (dtype == 0) return launch_t<double, true>(a, LP, panels_in_lds, lds_bytes, grid, s);
+    return launch_t<float, true>(a, LP, panels_in_lds, lds_bytes, grid, s);
 }
 
 }  // namespace rsvd

@@ -11,14 +11,26 @@ bytes/s of a kernel time measured apart (rocprofv3 --kernel-trace --stats -- pyt
 tools/batched_bench.py --fused-only ...).
 
     python tools/batched_bench.py --out profiles/batched_bench.json
+
+--compress: the rank-k compression (Engine.compress_tiles / compress_batched, k = l) over the same shapes.
+Per shape, alternating in one process: (a) the fused compression without the factors, (b) the same with
+them, and plain rsvd_tiles / rsvd_batched.  What a caller did before the compression existed -- (c):
+rsvd_tiles / rsvd_batched, a batched matmul rebuild in torch, the scatter into the image and the error
+norms -- is measured by a child process that imports the package from --parent-root, a built checkout of
+the parent commit (never the code under test), together with that checkout's plain rsvd_tiles /
+rsvd_batched.  The child is this file with --caller-rebuild --pkg-root DIR; it uses nothing the parent
+lacks.
+
+    python tools/batched_bench.py --compress --parent-root DIR --out profiles/compress_bench.json
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (name, kind, m, n, tile_m, tile_n, batch, l, q, dtype)
 SHAPES = [
@@ -34,9 +46,17 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fused-only", action="store_true", help="skip the loops (for a kernel-trace run)")
     ap.add_argument("--shapes", default="", help="comma-separated shape names (default: all)")
+    ap.add_argument("--compress", action="store_true", help="time the rank-k compression (see the module docstring)")
+    ap.add_argument("--parent-root", default="", help="--compress: a built checkout of the parent commit, for (c)")
+    ap.add_argument("--caller-rebuild", action="store_true",
+                    help="time rsvd_tiles / rsvd_batched + a torch rebuild, scatter and norms, and the plain call")
+    ap.add_argument("--pkg-root", default=REPO, help="the checkout to import the package from")
     args = ap.parse_args()
     if args.reps < 5:
         ap.error("--reps must be at least 5")
+    sys.path.insert(0, os.path.abspath(args.pkg_root))
+    if args.compress or args.caller_rebuild:
+        return compress_main(args)
 
     import torch
 
@@ -100,6 +120,118 @@ def main():
             rec["speedup_of_medians"] = rec["loop_median_ms"] / rec["fused_median_ms"]
             rec["margin_exceeds_spread"] = rec["fused_max_ms"] < rec["loop_min_ms"]
         rec["fused_end_to_end_bytes_per_s"] = rec["a_bytes_read"] / (rec["fused_median_ms"] * 1e-3)
+        print(json.dumps(rec), flush=True)
+        results.append(rec)
+    eng.close()
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(0), "results": results}, f, indent=1)
+        f.write("\n")
+
+
+def _stats(rec, key, ms):
+    rec[key + "_ms"] = ms
+    rec[key + "_median_ms"] = statistics.median(ms)
+    rec[key + "_min_ms"], rec[key + "_max_ms"] = min(ms), max(ms)
+
+
+def compress_main(args):
+    """--compress (the code under test: fused compression with and without factors, plain rSVD) and
+    --caller-rebuild (any checkout: the plain rSVD, and the rSVD followed by a torch rebuild)."""
+    import torch
+
+    import rsvd_kamaneh_raganato_terrana_amd as R
+
+    pkg = os.path.dirname(os.path.abspath(R.__file__))
+    assert os.path.dirname(pkg) == os.path.abspath(args.pkg_root), (pkg, args.pkg_root)
+    parent = {}
+    if args.compress and args.parent_root and not args.fused_only:
+        # the parent commit's numbers first, in a process of their own (this one has not touched the GPU yet)
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--caller-rebuild", "--pkg-root",
+                              args.parent_root, "--reps", str(args.reps), "--shapes", args.shapes, "--out", os.devnull],
+                             check=True, capture_output=True, text=True, timeout=600).stdout
+        parent = {r["shape"]: r for r in map(json.loads, filter(None, out.splitlines()))}
+    eng = R.Engine(0)
+    stream = torch.cuda.current_stream(0)
+    want = [s for s in args.shapes.split(",") if s]
+    results = []
+    for name, kind, m, n, tm, tn, batch, l, q, dt in SHAPES:
+        if want and name not in want:
+            continue
+        tdt = getattr(torch, dt)
+        k = l
+        gen = torch.Generator(device="cuda").manual_seed(1234)
+        assert eng.batched_is_fused(tm, tn, l, tdt, q=q, batch=batch) == 1, name
+        if kind == "tiles":
+            AT = torch.randn((n, m), generator=gen, device="cuda", dtype=tdt)
+            A = AT.t()  # column-major m x n
+            gr, gc = m // tm, n // tn
+            At = AT.view(gc, tn, gr, tm).permute(2, 0, 3, 1)  # (gr, gc, tm, tn) view of the tiles
+
+            def plain():
+                return eng.rsvd_tiles(A, tm, tn, l, q=q, seed=7, check_errors=False)
+
+            def caller():
+                U, S, V = plain()
+                Cb = (U[..., :k] * S[..., None, :k]) @ V[..., :k].transpose(-1, -2)
+                CT = torch.empty((n, m), device="cuda", dtype=tdt)
+                CT.view(gc, tn, gr, tm).copy_(Cb.permute(1, 3, 0, 2))  # the scatter back into the image
+                C = CT.t()
+                a2 = At.double().square().sum((-1, -2))
+                e2 = (At - Cb).double().square().sum((-1, -2))
+                return C, a2, e2
+        else:
+            A = torch.randn((batch, n, m), generator=gen, device="cuda", dtype=tdt).transpose(1, 2)
+
+            def plain():
+                return eng.rsvd_batched(A, l, q=q, seed=7, check_errors=False)
+
+            def caller():
+                U, S, V = plain()
+                C = (U[..., :k] * S[..., None, :k]) @ V[..., :k].transpose(-1, -2)
+                a2 = A.double().square().sum((-1, -2))
+                e2 = (A - C).double().square().sum((-1, -2))
+                return C, a2, e2
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            eng.sync()
+            return e0.elapsed_time(e1)
+
+        if args.caller_rebuild:
+            ways = [("rsvd", plain), ("caller_rebuild", caller)]
+        else:
+            Cout = torch.empty_like(A)
+            if kind == "tiles":
+                def comp(factors):
+                    return eng.compress_tiles(A, tm, tn, l, k=k, q=q, seed=7, out=Cout, return_factors=factors,
+                                              check_errors=False)
+            else:
+                def comp(factors):
+                    return eng.compress_batched(A, l, k=k, q=q, seed=7, out=Cout, return_factors=factors,
+                                                check_errors=False)
+            ways = [("compress", lambda: comp(False))]
+            if not args.fused_only:
+                ways += [("compress_factors", lambda: comp(True)), ("rsvd", plain)]
+        for _, fn in ways:  # warm-up: workspace, code objects, clocks
+            timed(fn)
+        ms = {key: [] for key, _ in ways}
+        for _ in range(args.reps):
+            for key, fn in ways:
+                ms[key].append(timed(fn))
+        rec = {"shape": name, "m": tm, "n": tn, "batch": batch, "l": l, "k": k, "q": q, "dtype": dt, "reps": args.reps}
+        for key in ms:
+            _stats(rec, key, ms[key])
+        if args.compress and name in parent:
+            for key in ("rsvd", "caller_rebuild"):
+                for suf in ("_ms", "_median_ms", "_min_ms", "_max_ms"):
+                    rec["parent_" + key + suf] = parent[name][key + suf]
+            # (a) not slower than (c); plain rSVD here within the spread the parent's own repetitions show
+            rec["compress_not_slower_than_caller_rebuild"] = rec["compress_median_ms"] <= rec["parent_caller_rebuild_median_ms"]
+            rec["rsvd_within_parent_spread"] = rec["rsvd_median_ms"] <= rec["parent_rsvd_max_ms"]
         print(json.dumps(rec), flush=True)
         results.append(rec)
     eng.close()
