@@ -21,7 +21,9 @@
  *   rsvd_compress_batched /        <- localMatrix = U * S.asDiagonal() * V.transpose() put back into the
  *   rsvd_lowrank /                    image (image_com.cpp:374, :381-394; Image::reconstruct :184-190) and
  *   rsvd_compress_host_f64            ||A - U diag(S) V^T||_F (tests/rSVD_test.cpp:77-95)
- * The C++ drop-in headers include/rSVD.hpp, include/QR.hpp, include/SVD_class.hpp sit on top of
+ *   rsvd_pod / rsvd_pod_host_f64   <- class POD: standard_POD / energy_POD / weight_POD, ns <= Nh branch
+ *                                     POD/ParametricDiffusion1D/src/POD.{hpp,cpp} (:136-224, :227-336, :339-462)
+ * The C++ drop-in headers include/rSVD.hpp, include/QR.hpp, include/SVD_class.hpp, include/POD.hpp sit on top of
  * these symbols with the reference's exact signatures.
  *
  * Layouts: every matrix is COLUMN-major (Eigen's default) with an explicit leading dimension.
@@ -38,7 +40,7 @@
 extern "C" {
 #endif
 
-#define RSVD_ABI_VERSION 8
+#define RSVD_ABI_VERSION 9
 
 typedef enum {
     RSVD_OK = 0,
@@ -353,6 +355,70 @@ int rsvd_lowrank(rsvd_handle_t h, int64_t m, int64_t n, int32_t k, int32_t dtype
 /* Host-only.  Device workspace bytes of rsvd_lowrank with an error (2 fp64 words per 64 x 64 tile of C). */
 int rsvd_lowrank_workspace_bytes(int64_t m, int64_t n, size_t *bytes);
 
+/* ---- POD (ABI 9): the snapshot method of the reference's class POD on the device --------------- */
+
+/* POD modes of a tall snapshot matrix S (nh x ns, ns <= nh), POD.cpp:136-462 (standard_POD, energy_POD,
+ * weight_POD; the ns > Nh branches are not covered).  Every step runs on the handle's stream:
+ *   T = Xh S                    when Xh (symmetric, not checked; CSR) is given, else T = S
+ *   C = D^1/2 S^T T D^1/2       ns x ns, ALWAYS fp64: fp32 S is widened on load (exact) and every product
+ *                               and sum runs on the f64 MFMA, split over row chunks and summed in a fixed
+ *                               order (no atomics), the lower triangle copied from the upper: C is
+ *                               bitwise symmetric, bit-reproducible and independent of the workspace's
+ *                               contents.  D = diag(d), d > 0 (NULL: ones); only diagonal D is supported
+ *                               (the reference's only caller passes 0.1 I, Diff1D_openmp.cpp:229-231)
+ *   small problem on C, fp64    svd_type (the reference's perform_SVD switch, POD.cpp:49-92):
+ *                               1 / 2 = rsvd_svd(C, Jacobi) -- 2 too: rsvd_svd's ParallelJacobi follows the
+ *                               reference's rotation path and its 1e-12 absolute stop, which leaves the
+ *                               vectors ~1e-5 from the SVD's, and W divides them by sigma_i;
+ *                               4 / 5 = rsvd_run(C, l = r, q, Jacobi / ParallelJacobi,
+ *                               Omega = rsvd_generate_omega(ns, r, seed, F64));
+ *                               0 / 3 (the power method) -> RSVD_ERR_UNSUPPORTED
+ *   rank rule, POD.cpp:203-216  on the first r values: den = sum sigma_i^2,
+ *                               while (I < 1 - tol^2 && N < r) { num += sigma_N^2; I = num / den; N++; }
+ *                               den == 0 gives N = 0; tol = 1 gives N = 0
+ *   W[:, i] = S D^1/2 V[:, i] / sigma_i, i < r (POD.cpp:172-174, :388-390); sigma_i == 0 -> a zero column
+ * All r columns of W are written and N comes back as one device word: the host slices W[:, :N] (the
+ * reference's conservativeResize).  Two quirks of the reference are the default: the modes are divided
+ * by sigma_i(C) (so they have length 1 / sigma_i(S)) and the rule weighs by sigma_i(C)^2 = sigma_i(S)^4.
+ * RSVD_POD_FLAG_TEXTBOOK divides by sqrt(sigma_i(C)) and weighs by sigma_i(C), as the book the reference
+ * cites: W is then Xh-orthonormal and the rule is the usual sum of sigma_i(S)^2. */
+#define RSVD_POD_FLAG_TEXTBOOK 1
+typedef struct {
+    int64_t nh, ns, lds;     /* S is nh x ns, column-major, lds >= nh; ns <= nh, ns <= 4096             */
+    int32_t r;               /* modes computed, 1 .. ns (the reference's r)                               */
+    int32_t dtype;           /* RSVD_F64 / RSVD_F32: type of S, Xh's values and W                         */
+    int32_t svd_type;        /* the reference's 0..5 (POD.cpp:49-92); 1, 2, 4, 5 supported                */
+    int32_t q;               /* power iterations of svd_type 4 / 5                                        */
+    int32_t flags, reserved; /* RSVD_POD_FLAG_*                                                           */
+    uint64_t seed;           /* Omega of svd_type 4 / 5 = rsvd_generate_omega(ns, r, seed, F64)           */
+    double tol;              /* 0 <= tol <= 1                                                             */
+} rsvd_pod_desc_t;
+/* Xh in CSR, device pointers: rowptr nh + 1 entries, colind and val (S's type) nnz entries. */
+typedef struct {
+    const int32_t *rowptr, *colind;
+    const void *val;
+    int64_t nnz;
+} rsvd_csr_t;
+
+/* S is read in place: any lds >= nh, any element-aligned base.  W: nh x r, ldw >= nh, S's type; rows nh ..
+ * ldw are not touched.  sigma: ns fp64 words on the device -- fp64 also for fp32 S, since they are the
+ * singular values of the fp64 C: all ns (svd_type 1 / 2, the reference's sigma = getS()) or the first r
+ * (4 / 5) are written, the rest zeroed.  N: one device int32.  C (nullable): ns x ns fp64, ld ns, the
+ * weighted correlation matrix as the small solver saw it.  Asynchronous; nothing synchronises.
+ * RSVD_ERR_INVALID_ARG: r outside 1 .. ns, lds < nh, ldw < nh, tol outside [0, 1] or NaN, svd_type outside
+ * 0 .. 5, unknown flags, q < 0, NULL S / W / sigma / N, nnz < 0.  RSVD_ERR_UNSUPPORTED: ns > nh, ns > 4096,
+ * svd_type 0 / 3, dtype BF16 / FP8_E4M3, a row-sharded handle. */
+int rsvd_pod(rsvd_handle_t h, const rsvd_pod_desc_t *desc, const void *S, const rsvd_csr_t *Xh /* nullable */,
+             const double *d /* nullable, device, ns */, void *W, int64_t ldw /* nh x r */,
+             double *sigma /* device, ns words */, int32_t *N /* device, 1 word */,
+             double *C /* nullable, device, ns x ns, ld ns */);
+/* Host-only, with rsvd_pod's descriptor checks and codes.  Device workspace bytes of rsvd_pod: its own
+ * region (T when has_xh, the chunk slabs, C, the small factors, Z) followed by the nested solver's. */
+int rsvd_pod_workspace_bytes(const rsvd_pod_desc_t *desc, int has_xh, size_t *bytes);
+/* Host-only.  The split of the correlation kernel: upper 32 x 32 block pairs of C and row chunks -- a
+ * function of (nh, ns, dtype) alone. */
+int rsvd_pod_plan(const rsvd_pod_desc_t *desc, int32_t *tiles, int32_t *chunks);
+
 /* ---- host-pointer fp64 entry points used by the C++ drop-in headers (synchronous) --------- */
 int rsvd_run_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, int64_t lda, int32_t l,
                       int32_t q, int32_t method, const double *omega /* nullable, n x l, ld n */,
@@ -375,6 +441,13 @@ int rsvd_svd_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, in
 int rsvd_compress_host_f64(rsvd_handle_t h, int64_t m, int64_t n, const double *A, int64_t lda, int32_t tile_m,
                            int32_t tile_n, int32_t l, int32_t k, int32_t q, uint64_t seed, double *C, int64_t ldc,
                            double *err2 /* host, 2 per tile, nullable */);
+
+/* class POD's numeric core on host buffers (include/POD.hpp): S nh x ns (ld desc->lds), Xh as host CSR
+ * (rowptr NULL: none), d host (nullable); desc->dtype is taken as RSVD_F64.  W: nh x r, ld nh (all r
+ * columns), sigma: ns, *N: the rank rule's N. */
+int rsvd_pod_host_f64(rsvd_handle_t h, const rsvd_pod_desc_t *desc, const double *S, const int32_t *rowptr,
+                      const int32_t *colind, const double *val, int64_t nnz, const double *d /* nullable, ns */,
+                      double *W, double *sigma, int32_t *N);
 
 #ifdef __cplusplus
 }

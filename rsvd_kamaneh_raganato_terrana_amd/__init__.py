@@ -1,12 +1,13 @@
 """rsvd_kamaneh_raganato_terrana_amd -- MI355X-native randomized SVD.
 
-Drop-in for the rSVD() / intermediate_step() / generateOmega() / QR() / SVD<method> path of
+Drop-in for the rSVD() / intermediate_step() / generateOmega() / QR() / SVD<method> / POD path of
 AMSC22-23/rSVD_Kamaneh_Raganato_Terrana: a C ABI (include/rsvd_c.h, librsvd_hip.so) over
 hand-written gfx950 HIP kernels; this package is the Python host front end over that ABI.
 """
 from ._capi import build, row_partition, RSVDError, LIB_PATH  # noqa: F401
 from .api import (  # noqa: F401
     Engine,
+    POD,
     QRMode,
     SVD,
     SVDMethod,
@@ -18,6 +19,7 @@ from .api import (  # noqa: F401
     intermediate_step,
     make_allreduce_hook,
     make_collective_hook,
+    pod_rank,
     qr_decomposition_full,
     qr_decomposition_reduced,
     rSVD,
@@ -31,4 +33,5 @@ __all__ = [
     "make_collective_hook", "rSVD",
     "rSVD_image_compression",
     "SVD", "qr_decomposition_full", "qr_decomposition_reduced",
+    "POD", "pod_rank",
 ]

@@ -31,6 +31,7 @@ SVD_JACOBI, SVD_POWER, SVD_PARALLEL_JACOBI, SVD_POWER_IC = 0, 1, 2, 3
 QR_AUTO, QR_GS2, QR_CHOLQR2 = 0, 1, 2
 FLAG_LOWP_INTERMEDIATES = 1
 FLAG_FORCE_NSHARD = 2  # test/diagnostic: the n-side sharded path (RCCL calls) at world 1
+POD_FLAG_TEXTBOOK = 1  # rsvd_pod: divide by sqrt(sigma_i(C)), weigh the rank rule by sigma_i(C)
 COMM_ID_BYTES = 128
 
 # Every symbol include/rsvd_c.h declares (checked by tests/test_capi_exports.py).
@@ -45,6 +46,7 @@ EXPORTS = (
     "rsvd_run_batched", "rsvd_batched_workspace_bytes", "rsvd_batched_is_fused",
     "rsvd_compress_batched", "rsvd_compress_workspace_bytes", "rsvd_lowrank", "rsvd_lowrank_workspace_bytes",
     "rsvd_compress_host_f64",
+    "rsvd_pod", "rsvd_pod_workspace_bytes", "rsvd_pod_plan", "rsvd_pod_host_f64",
 )
 
 
@@ -90,6 +92,23 @@ class CompressDesc(ctypes.Structure):
     ]
 
 
+class PodDesc(ctypes.Structure):
+    """rsvd_pod_desc_t (include/rsvd_c.h, ABI 9)."""
+    _fields_ = [
+        ("nh", ctypes.c_int64), ("ns", ctypes.c_int64), ("lds", ctypes.c_int64),
+        ("r", ctypes.c_int32), ("dtype", ctypes.c_int32), ("svd_type", ctypes.c_int32), ("q", ctypes.c_int32),
+        ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("tol", ctypes.c_double),
+    ]
+
+
+class Csr(ctypes.Structure):
+    """rsvd_csr_t (include/rsvd_c.h, ABI 9): device pointers of a CSR matrix."""
+    _fields_ = [
+        ("rowptr", ctypes.c_void_p), ("colind", ctypes.c_void_p), ("val", ctypes.c_void_p), ("nnz", ctypes.c_int64),
+    ]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                 ctypes.c_void_p, ctypes.c_void_p)
 # rsvd_collective_fn(op, send, recv, count, dtype, stream, user) -- ABI 5
@@ -101,9 +120,9 @@ COLL_REDUCE_SCATTER, COLL_ALL_GATHER = 1, 2
 def _sources():
     """The files librsvd_hip.so is built from, in the order the Makefile hashes them."""
     hip = ("util.hip proj.hip qr.hip jacobi.hip wide_proj.hip wide_gram.hip wide_chol.hip wide_panel.hip wide_svd.hip "
-           "wide_eig.hip dense.hip gemm.hip batched.hip lowrank.hip").split()
-    cpp = "driver.cpp wide.cpp wide_plan.cpp dense_api.cpp comm.cpp dense_big.cpp batched_run.cpp".split()
-    hdr = "common.hpp kernels.hpp wide.hpp wide_dev.hpp dense.hpp handle.hpp batched.hpp lowrank.hpp".split()
+           "wide_eig.hip dense.hip gemm.hip batched.hip lowrank.hip pod.hip").split()
+    cpp = "driver.cpp wide.cpp wide_plan.cpp dense_api.cpp comm.cpp dense_big.cpp batched_run.cpp pod.cpp".split()
+    hdr = "common.hpp kernels.hpp wide.hpp wide_dev.hpp dense.hpp handle.hpp batched.hpp lowrank.hpp pod.hpp".split()
     return ([os.path.join(CSRC, f) for f in hip + cpp + hdr] + [os.path.join(REPO, "include", "rsvd_c.h")]
             + [os.path.join(CSRC, "Makefile")])
 
@@ -201,6 +220,11 @@ def lib():
     L.rsvd_lowrank.argtypes = [vp, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, ctypes.c_double, vp]
     L.rsvd_lowrank_workspace_bytes.argtypes = [i64, i64, szp]
     L.rsvd_compress_host_f64.argtypes = [vp, i64, i64, dp, i64, i32, i32, i32, i32, i32, u64, dp, i64, dp]
+    pp = ctypes.POINTER(PodDesc)
+    L.rsvd_pod.argtypes = [vp, pp, vp, ctypes.POINTER(Csr), vp, vp, i64, vp, vp, vp]
+    L.rsvd_pod_workspace_bytes.argtypes = [pp, ctypes.c_int, szp]
+    L.rsvd_pod_plan.argtypes = [pp, ip, ip]
+    L.rsvd_pod_host_f64.argtypes = [vp, pp, dp, ip, ip, dp, i64, dp, dp, dp, ip]
     _LIB = L
     return L
 

@@ -658,6 +658,122 @@ class Engine:
             return C
         return err if C is None else (C, err)
 
+    # -- POD (rsvd_pod, include/rsvd_c.h ABI 9) ---------------------------------------------------
+    @staticmethod
+    def _pod_desc(nh: int, ns: int, lds: int, r: int, dtype: int, svd_type: int, q: int, seed: int, tol: float,
+                  textbook: bool) -> "_capi.PodDesc":
+        return _capi.PodDesc(nh=nh, ns=ns, lds=lds, r=r, dtype=dtype, svd_type=int(svd_type), q=q,
+                             flags=_capi.POD_FLAG_TEXTBOOK if textbook else 0, reserved=0, seed=seed, tol=tol)
+
+    def pod_plan(self, nh: int, ns: int, dtype=_capi.F64, r: int = 1):
+        """rsvd_pod_plan: (upper 32 x 32 block pairs of C, row chunks) of the correlation kernel for an
+        nh x ns S -- host arithmetic, a function of (nh, ns, dtype) alone."""
+        dt = dtype if isinstance(dtype, int) else self.abi_dtype(dtype)
+        pd = self._pod_desc(nh, ns, nh, r, dt, 4, 2, 0, 0.0, False)
+        tiles, chunks = ctypes.c_int32(0), ctypes.c_int32(0)
+        check(lib().rsvd_pod_plan(ctypes.byref(pd), ctypes.byref(tiles), ctypes.byref(chunks)))
+        return tiles.value, chunks.value
+
+    def pod(self, S, r: int, tol: float, Xh=None, d=None, svd_type: int = 4, q: int = 2, seed: int = 0,
+            textbook: bool = False, return_corr: bool = False, out=None, truncate: bool = True):
+        """POD modes of the snapshot matrix S (nh x ns CUDA, column-major float64 / float32, ns <= nh), the
+        snapshot method of the reference's class POD (POD.cpp:136-462) on the device: C = D^1/2 S^T Xh S
+        D^1/2 in fp64 by the split-K correlation kernel, the small SVD (svd_type 1 / 2) or rSVD (4 / 5, width
+        r, q power iterations, Omega = Philox(seed)) of C in fp64, the reference's rank rule, and
+        W[:, i] = S D^1/2 V[:, i] / sigma_i.  S is read in place (any leading dimension, any storage offset).
+        Xh: a torch sparse-CSR tensor or a (rowptr, colind, val) triple (indices are cast to int32, values to
+        S's dtype); d: ns positive weights (the diagonal of D).  textbook: RSVD_POD_FLAG_TEXTBOOK.
+        out: a column-major nh x r tensor for W (any leading dimension >= nh).
+        Returns (W[:, :N], sigma, N) -- sigma float64 with ns entries, N an int; this reads N back and is the
+        one place that synchronises -- with C (ns x ns float64) appended when return_corr.  truncate=False
+        returns the full W and N as a device int32 tensor without synchronising."""
+        torch = _torch()
+        if S.dim() != 2:
+            raise ValueError("expected a matrix")
+        if S.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"unsupported dtype {S.dtype}")
+        S, lds = colmajor(S)
+        nh, ns = S.shape
+        lds = max(lds, nh) if ns > 1 else nh
+        dev = S.device
+        pd = self._pod_desc(nh, ns, lds, int(r), self.abi_dtype(S.dtype), svd_type, q, seed, float(tol), textbook)
+        nbytes = ctypes.c_size_t(0)
+        check(lib().rsvd_pod_workspace_bytes(ctypes.byref(pd), int(Xh is not None), ctypes.byref(nbytes)))
+        csr, keep = None, None
+        if Xh is not None:
+            if _is_torch(Xh):
+                rowptr, colind, val = Xh.crow_indices(), Xh.col_indices(), Xh.values()
+            else:
+                rowptr, colind, val = Xh
+            rowptr = torch.as_tensor(rowptr).to(device=dev, dtype=torch.int32).contiguous()
+            colind = torch.as_tensor(colind).to(device=dev, dtype=torch.int32).contiguous()
+            val = torch.as_tensor(val).to(device=dev, dtype=S.dtype).contiguous()
+            if rowptr.numel() != nh + 1 or colind.numel() != val.numel():
+                raise ValueError("Xh must be nh x nh in CSR: nh + 1 row pointers, as many column indices as values")
+            keep = (rowptr, colind, val)
+            csr = _capi.Csr(rowptr=rowptr.data_ptr(), colind=colind.data_ptr(), val=val.data_ptr(), nnz=val.numel())
+        dv = None
+        if d is not None:
+            dv = torch.as_tensor(d).to(device=dev, dtype=torch.float64).contiguous()
+            if dv.dim() != 1 or dv.numel() != ns:
+                raise ValueError("d must hold ns weights")
+        W = empty_colmajor(nh, r, S.dtype, dev) if out is None else out
+        ldw = self._check_out(W, nh, r, S.dtype, "W")
+        sigma = torch.empty(ns, dtype=torch.float64, device=dev)
+        N = torch.empty(1, dtype=torch.int32, device=dev)
+        C = torch.empty((ns, ns), dtype=torch.float64, device=dev) if return_corr else None
+        self._reserve_bytes(nbytes.value)
+        self._bind_stream()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        check(lib().rsvd_pod(self.h, ctypes.byref(pd), ptr(S), ctypes.byref(csr) if csr is not None else None,
+                             ptr(dv), ptr(W), ldw, ptr(sigma), ptr(N), ptr(C)), self.h)
+        del keep
+        if not truncate:
+            return (W, sigma, N, C) if return_corr else (W, sigma, N)
+        self.sync()
+        n = int(N.item())
+        return (W[:, :n], sigma, n, C) if return_corr else (W[:, :n], sigma, n)
+
+    def pod_host(self, S: np.ndarray, r: int, tol: float, Xh=None, d=None, svd_type: int = 4, q: int = 2,
+                 seed: int = 0, textbook: bool = False):
+        """pod() for numpy input through rsvd_pod_host_f64 (what include/POD.hpp calls): S float64, Xh a
+        dense nh x nh array (exact zeros dropped) or a (rowptr, colind, val) triple, d the ns weights.
+        Returns (W[:, :N], sigma, N)."""
+        S = np.asfortranarray(S, dtype=np.float64)
+        nh, ns = S.shape
+        pd = self._pod_desc(nh, ns, nh, int(r), _capi.F64, svd_type, q, seed, float(tol), textbook)
+        nbytes = ctypes.c_size_t(0)
+        check(lib().rsvd_pod_workspace_bytes(ctypes.byref(pd), int(Xh is not None), ctypes.byref(nbytes)))
+        rp = ci = va = None
+        nnz = 0
+        if Xh is not None:
+            if isinstance(Xh, tuple):
+                rp, ci, va = Xh
+            else:
+                rp, ci, va = dense_to_csr(np.asarray(Xh, dtype=np.float64))
+            rp = np.ascontiguousarray(rp, dtype=np.int32)
+            ci = np.ascontiguousarray(ci, dtype=np.int32)
+            va = np.ascontiguousarray(va, dtype=np.float64)
+            if rp.size != nh + 1 or ci.size != va.size:
+                raise ValueError("Xh must be nh x nh in CSR: nh + 1 row pointers, as many column indices as values")
+            nnz = va.size
+        dv = None
+        if d is not None:
+            dv = np.ascontiguousarray(d, dtype=np.float64)
+            if dv.ndim != 1 or dv.size != ns:
+                raise ValueError("d must hold ns weights")
+        W = np.zeros((nh, r), order="F")
+        sigma = np.zeros(ns)
+        N = ctypes.c_int32(0)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if a is not None else None
+        self._reserve_bytes(nbytes.value)
+        self._bind_stream()
+        check(lib().rsvd_pod_host_f64(self.h, ctypes.byref(pd), _dp(S), ip(rp), ip(ci),
+                                      _dp(va) if va is not None else None, nnz,
+                                      _dp(dv) if dv is not None else None, _dp(W), _dp(sigma), ctypes.byref(N)),
+              self.h)
+        return W[:, :N.value].copy(order="F"), sigma, N.value
+
     def range_finder(self, A, omega, q: int = 2, qr_mode: int = QRMode.Auto, out=None):
         """Device intermediate_step: the orthonormal range basis Q (m x l).  out: a column-major
         m x l tensor to write Q into (any leading dimension >= m), as rsvd's out=."""
@@ -826,6 +942,40 @@ def compression_ratio(m: int, n: int, l: int) -> float:
     return m * n / (l * (m + n + 1))
 
 
+def pod_rank(sigma, tol: float, textbook: bool = False) -> int:
+    """The reference's rank rule (POD.cpp:203-216) on the values `sigma` (its first r): the smallest N
+    whose running share of sum sigma_i^2 reaches 1 - tol^2, by the reference's loop
+        while (I < 1 - tol^2 && N < r) { num += sigma_N^2; I = num / den; N++; }
+    in float64.  A zero sum keeps no mode (N = 0), as rsvd_pod.  textbook: weigh by sigma_i instead of
+    sigma_i^2 (RSVD_POD_FLAG_TEXTBOOK: sigma_i of the correlation matrix is sigma_i(S)^2 already)."""
+    w = [float(s) if textbook else float(s) * float(s) for s in np.asarray(sigma, dtype=np.float64).ravel()]
+    den = 0.0
+    for x in w:
+        den += x
+    if den == 0.0:
+        return 0
+    thr = 1.0 - float(tol) * float(tol)
+    N, I, num = 0, 0.0, 0.0
+    while I < thr and N < len(w):
+        num += w[N]
+        I = num / den
+        N += 1
+    return N
+
+
+def dense_to_csr(X: np.ndarray):
+    """(rowptr, colind, val) of a dense square matrix, exact zeros dropped (what include/POD.hpp does to the
+    reference's dense Xh)."""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("expected a matrix")
+    mask = X != 0
+    rowptr = np.zeros(X.shape[0] + 1, dtype=np.int32)
+    rowptr[1:] = np.cumsum(mask.sum(axis=1))
+    rows, cols = np.nonzero(mask)  # row-major order: each row's entries by ascending column
+    return rowptr, cols.astype(np.int32), np.ascontiguousarray(X[rows, cols])
+
+
 def default_engine() -> Engine:
     global _DEFAULT
     if _DEFAULT is None:
@@ -953,3 +1103,64 @@ class SVD:
 
     def getV(self):
         return self._V
+
+
+class POD:
+    """class POD (POD/ParametricDiffusion1D/src/POD.hpp:24-49) on the GPU engine: ``.W`` holds the POD
+    basis (Nh x N) and ``.sigma`` the singular values.  The reference's four constructors map to
+
+    * ``POD(S, r, svd_type=...)``                       naive: the SVD / rSVD of S itself (POD.cpp:116-133)
+    * ``POD(S, r, tol, svd_type=...)``                  standard_POD (:136-224)
+    * ``POD(S, r, tol, Xh=Xh, svd_type=...)``           energy_POD (:227-336)
+    * ``POD(S, r, tol, Xh=Xh, D=D, svd_type=...)``      weight_POD (:339-462); D a vector of weights or a
+      diagonal matrix (a non-diagonal D raises ValueError)
+
+    svd_type is the reference's 0..5 (POD.cpp:49-92).  The three snapshot-method variants need ns <= Nh
+    and svd_type 1, 2, 4 or 5 (ValueError otherwise); S may be a numpy array or a CUDA tensor.  Nothing is
+    printed.  ``N`` is the rank the rule kept; ``textbook`` selects RSVD_POD_FLAG_TEXTBOOK."""
+
+    def __init__(self, S=None, r: int = 0, tol: Optional[float] = None, svd_type: int = 4, Xh=None, D=None,
+                 q: int = 2, seed: int = 0, textbook: bool = False):
+        self.W = self.sigma = None
+        self.N = 0
+        if S is None:  # the default constructor
+            return
+        if not 0 <= int(svd_type) <= 5:
+            raise ValueError("The svd_type should be in [0,5].")
+        if tol is None:
+            if Xh is not None or D is not None:
+                raise ValueError("Xh and D need a tolerance (the naive POD takes neither)")
+            self.W, self.sigma = self._naive(S, int(r), int(svd_type), seed)
+            self.N = self.W.shape[1]
+            return
+        nh, ns = S.shape
+        if ns > nh:
+            raise ValueError("ns > Nh (the reference's K = S S^T branch) is not supported")
+        if int(svd_type) in (0, 3):
+            raise ValueError("svd_type 0 / 3 (power method) is not supported by the snapshot-method POD")
+        d = None
+        if D is not None:
+            Dn = D.detach().cpu().numpy() if _is_torch(D) else np.asarray(D, dtype=np.float64)
+            if Dn.ndim == 2:
+                if Dn.shape != (ns, ns) or np.any(Dn - np.diag(np.diag(Dn)) != 0):
+                    raise ValueError("D must be an ns x ns diagonal matrix")
+                Dn = np.diag(Dn)
+            d = np.ascontiguousarray(Dn, dtype=np.float64)
+        eng = default_engine()
+        if _is_torch(S):
+            self.W, self.sigma, self.N = eng.pod(S, r, tol, Xh=Xh, d=d, svd_type=svd_type, q=q, seed=seed,
+                                                 textbook=textbook)
+        else:
+            self.W, self.sigma, self.N = eng.pod_host(S, r, tol, Xh=Xh, d=d, svd_type=svd_type, q=q, seed=seed,
+                                                      textbook=textbook)
+
+    @staticmethod
+    def _naive(S, r: int, svd_type: int, seed: int):
+        """perform_SVD on S itself (POD.cpp:42-114): SVD<method> for 0..2, rSVD(S, r, method) for 3..5."""
+        method = (SVDMethod.Power, SVDMethod.Jacobi, SVDMethod.ParallelJacobi)[svd_type % 3]
+        if svd_type >= 3:
+            U, s, _ = rSVD(S, r, method, seed=seed)
+            return U, s
+        sv = SVD(S.detach().cpu().numpy() if _is_torch(S) else S, r=r if svd_type == 0 else 0, method=method, seed=seed)
+        sv.compute()
+        return sv.getU(), sv.getS()
