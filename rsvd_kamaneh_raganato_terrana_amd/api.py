@@ -372,7 +372,7 @@ class Engine:
             elif om.dim() == 3 and om.shape[0] == batch:
                 if not (om.stride(1) == 1 and om.stride(2) >= max(1, om.shape[1])):
                     om = om.transpose(1, 2).contiguous().transpose(1, 2)
-                ldo = om.stride(2)
+                ldo = max(om.stride(2), d.n)  # l == 1: the stride of the one-column dimension carries no meaning
                 bd.omega_stride = om.stride(0) if batch > 1 else 0
             else:
                 raise ValueError("omega must be (n, l) or (batch, n, l)")
@@ -483,7 +483,7 @@ class Engine:
             elif om.dim() == 3 and om.shape[0] == batch:
                 if not (om.stride(1) == 1 and om.stride(2) >= max(1, om.shape[1])):
                     om = om.transpose(1, 2).contiguous().transpose(1, 2)
-                ldo = om.stride(2)
+                ldo = max(om.stride(2), d.n)  # l == 1: the stride of the one-column dimension carries no meaning
                 bd.omega_stride = om.stride(0) if batch > 1 else 0
             else:
                 raise ValueError("omega must be (n, l) or (batch, n, l)")

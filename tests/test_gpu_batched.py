@@ -10,7 +10,15 @@ Omega_b = oracle.generate_omega(n, l, 99 + b).  Every case asserts batched_is_fu
 kernel ran, not the loop) unless it is about the loop.  The shapes are the smallest at which each
 thing can go wrong: l == m == n, l < 16 in a padded LP, odd sizes, one side past 64 rows (more than
 one row per lane of a reflector), 256 x 256 x 64 fp64 (panels in the workspace instead of LDS), and
-more matrices than one launch has workgroups' worth of compute units."""
+more matrices than one launch has workgroups' worth of compute units.
+
+test_parity_every_instantiation runs the rows of tests/batched_cases.py (B = 2, an Omega per matrix, the
+same bars): every (type, LP, panel location) the kernel can be launched with, LP = 48 (384 threads) among
+them, odd l above 16, l = 1 (where the single column is compared: k = max(1, l // 2)) and both sides of the
+two LDS budgets.  Measured on an MI355X over those rows: fp64 S 8.6e-15, U and V 3.4e-14, orthonormality
+1.5e-13; fp32 S 7.5e-6 (64 x 64 x 64, last singular value 3.5e-5), U and V 8.9e-7, orthonormality 6.8e-6.
+Found with it: Engine.rsvd_batched / compress_batched passed the stride of Omega's one-column dimension as
+its leading dimension at l = 1, and 9 x 7 x 1 with an Omega per matrix was refused as an invalid argument."""
 import ctypes
 import functools
 
@@ -18,6 +26,7 @@ import numpy as np
 import pytest
 
 import oracle
+import batched_cases as bc
 from conftest import gapped_matrix, rel_fro, sign_align
 from ws_patterns import PATTERNS
 
@@ -76,7 +85,7 @@ def _host(*ts):
 def _parity(tag, U, S, V, ref, l, f32):
     Uo, So, Vo = ref
     tol_s, tol_v, tol_o = (1e-4, 1e-4, 1e-4) if f32 else (1e-10, 1e-8, 1e-10)
-    k = l // 2
+    k = max(1, l // 2)  # l = 1: the single column
     es = rel_fro(S, So)
     eu = rel_fro(sign_align(U[:, :k], Uo[:, :k]), Uo[:, :k])
     ev = rel_fro(sign_align(V[:, :k], Vo[:, :k]), Vo[:, :k])
@@ -105,6 +114,32 @@ def test_parity(engine, m, n, l, q, f32, shared):
     U, S, V = _host(U, S, V)
     for b in range(B):
         _parity(f"{m}x{n} l{l} q{q} b{b}", U[b], S[b], V[b], _ref(m, n, l, q, b, 0 if shared else b, f32), l, f32)
+
+
+# ---- 1b. every reachable instantiation ------------------------------------------------------------
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+@pytest.mark.parametrize("m,n,l,q", bc.CASES, ids=[bc.case_id(c) for c in bc.CASES])
+def test_parity_every_instantiation(engine, m, n, l, q, f32):
+    """The rows of tests/batched_cases.py: between them and the two types every (T, LP, panel location) the
+    kernel can be launched with runs (tests/test_batched_cases.py checks that on the CPU), with odd l above
+    16 (the Jacobi dummy column), l = 1, l = LP = 48 and 64, and the shapes on both sides of each LDS budget."""
+    torch = _torch()
+    B = 2
+    assert engine.batched_is_fused(m, n, l, _tdt(f32), q=q, batch=B) == 1
+    t, LP, loc = bc.placement(m, n, l, q, f32, batch=B)
+    for pt, inside, past in bc.BUDGET_PAIRS:
+        if pt == t and (m, n, l, q) == inside:
+            assert bc.workspace_bytes(m, n, l, q, f32, batch=B) == bc.LDS_FLOOR and loc == "lds"
+        if pt == t and (m, n, l, q) == past:
+            assert bc.workspace_bytes(m, n, l, q, f32, batch=B) > bc.LDS_FLOOR and loc == "ws"
+    A = _dev_batch([_matrix(m, n, l, b, f32) for b in range(B)], f32)
+    om = torch.from_numpy(np.stack([_omega(n, l, b, f32) for b in range(B)])).to(_tdt(f32))
+    U, S, V, info = engine.rsvd_batched(A, l, q=q, omega=om, return_info=True)
+    assert U.shape == (B, m, l) and S.shape == (B, l) and V.shape == (B, n, l) and U.dtype == _tdt(f32)
+    assert not bool((info[:, 1] & 2).any())
+    U, S, V = _host(U, S, V)
+    for b in range(B):
+        _parity(f"{t} LP{LP} {loc} {m}x{n} l{l} q{q} b{b}", U[b], S[b], V[b], _ref(m, n, l, q, b, b, f32), l, f32)
 
 
 # ---- 2. Philox seeds ---------------------------------------------------------------------------
@@ -260,7 +295,8 @@ def test_more_matrices_than_compute_units(engine):
 
 
 # ---- 8. workspace contents ---------------------------------------------------------------------
-@pytest.mark.parametrize("m,n,l,q", [(70, 45, 8, 2), (256, 256, 64, 1)], ids=["panels-in-lds", "panels-in-workspace"])
+@pytest.mark.parametrize("m,n,l,q", [(70, 45, 8, 2), (256, 256, 64, 1), (150, 125, 48, 1)],
+                         ids=["panels-in-lds", "panels-in-workspace", "lp48-panels-in-workspace"])
 def test_workspace_contents_do_not_matter(engine, m, n, l, q):
     torch = _torch()
     B = 6

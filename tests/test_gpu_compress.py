@@ -13,10 +13,17 @@ Bars (none of them taken from what the code gives):
                 relative: m n <= 65536 non-negative fp64 terms, (m n + 3) 2^-53 ~ 7e-12
   Pythagoras    |err1 - (err0 - sum_{i<k} S_i^2)| <= tol err0, tol 1e-10 (fp64), 1e-4 (fp32): C_k is an
                 orthogonal projection of A; the bars are the project's orthonormality bars
+
+test_parity_every_instantiation holds the rows of tests/batched_cases.COMPRESS_CASES to the same four checks:
+the compress tail at LP 32, 48 and 64 in both types and both panel locations, at ranks whose ceil(k / 8)
+does not divide the workgroup.  Measured on an MI355X over those rows: parity 2.2e-14 (fp64), 7.5e-6 (fp32,
+64 x 64 x 64; 8.2e-7 elsewhere); factors 2.0e-16, 7.0e-8; Pythagoras 1.2e-14, 3.9e-7.  lowrank.hip on its own
+is in tests/test_gpu_lowrank.py.
 """
 import numpy as np
 import pytest
 
+import batched_cases as bc
 import test_gpu_batched as TB
 from conftest import rel_fro
 from padded import _Padded
@@ -55,15 +62,12 @@ def _check_err_words(tag, err, A, C, rtol=1e-10):
 
 
 # ---- 1-4. parity, consistency with the call's own factors, the error words, the known answer --------
-@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
-@pytest.mark.parametrize("m,n,l,q", SHAPES)
-def test_parity_consistency_and_error_words(engine, m, n, l, q, f32):
-    B = 3
+def _four_checks(engine, m, n, l, q, f32, B, ks):
     assert engine.batched_is_fused(m, n, l, _tdt(f32), q=q, batch=B) == 1
     A = _dev_batch([_matrix(m, n, l, b, f32) for b in range(B)], f32)
     om = _om_batch(n, l, range(B), f32)
     tol_p, tol_c, tol_o = (1e-4, 1e-5, 1e-4) if f32 else (1e-8, 1e-12, 1e-10)
-    for k in _ks(l):
+    for k in ks:
         C, err, (U, S, V) = engine.compress_batched(A, l, k=k, q=q, omega=om, return_factors=True)
         assert C.shape == (B, m, n) and C.dtype == _tdt(f32) and C.stride(1) == 1
         assert err.shape == (B, 2) and err.dtype == _torch().float64
@@ -79,6 +83,29 @@ def test_parity_consistency_and_error_words(engine, m, n, l, q, f32):
             assert py <= tol_o, (k, b, py)
             if l == m == n == k:  # the known answer: all of a full-rank square matrix
                 assert err[b, 1] <= tol_o * err[b, 0], (b, err[b])
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+@pytest.mark.parametrize("m,n,l,q", SHAPES)
+def test_parity_consistency_and_error_words(engine, m, n, l, q, f32):
+    _four_checks(engine, m, n, l, q, f32, 3, _ks(l))
+
+
+def _ks_wide(l):
+    """_ks(l) and the ranks below l at which ceil(k / 8) = 3, 5, 6, 7 does not divide the workgroup: the
+    round of scale_panel then leaves a spare group of threads (ch == nch) beside the working ones."""
+    return sorted(set(_ks(l)) | {k for k in (17, 33, 41, 49) if k < l})
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+@pytest.mark.parametrize("m,n,l,q", bc.COMPRESS_CASES, ids=[bc.case_id(c) for c in bc.COMPRESS_CASES])
+def test_parity_every_instantiation(engine, m, n, l, q, f32):
+    """The compress tail at LP 32, 48 and 64 in both types and both panel locations (the rows of
+    tests/batched_cases.py; where each runs is checked on the CPU by tests/test_batched_cases.py), with odd
+    l, more panel rows than one round of scale_panel holds (200 and 256 rows) and the ranks of _ks_wide."""
+    t, LP, loc = bc.placement(m, n, l, q, f32, batch=2)
+    print(f"COMPRESS {m}x{n} l{l}: {t} LP{LP} panels in {loc}, k in {_ks_wide(l)}")
+    _four_checks(engine, m, n, l, q, f32, 2, _ks_wide(l))
 
 
 def test_parity_panels_in_workspace(engine):
@@ -100,8 +127,9 @@ def test_parity_panels_in_workspace(engine):
 
 
 # ---- 5. the factors are rsvd_batched's; C and err do not depend on asking for them ---------------------
-@pytest.mark.parametrize("m,n,l,q,f32", [(70, 45, 8, 2, False), (33, 17, 5, 1, True), (256, 256, 64, 2, False)],
-                         ids=["f64", "f32", "panels-in-workspace"])
+@pytest.mark.parametrize("m,n,l,q,f32", [(70, 45, 8, 2, False), (33, 17, 5, 1, True), (256, 256, 64, 2, False),
+                                         (90, 50, 33, 2, True), (200, 100, 47, 1, False)],
+                         ids=["f64", "f32", "panels-in-workspace", "f32-lp48", "f64-lp48-panels-in-workspace"])
 def test_factors_untouched(engine, m, n, l, q, f32):
     torch = _torch()
     B = 3 if m < 256 else 2

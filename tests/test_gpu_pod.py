@@ -22,7 +22,11 @@ nh 2^-53 || |S|^T |T| ||_F / || S^T T ||_F is computed from the reference and ha
 of it); sigma and W 1e-8 (fp64) / 1e-4 (fp32), test_gpu_batched.py's parity bars; W^T Xh W - I 1e-10 /
 1e-4 with the textbook flag.  N is compared only after the reference's running shares are shown to stay
 >= 1e-6 away from 1 - tol^2 (for the shares I_1 .. I_{r-1}: the comparison of I_r cannot change N, the
-loop stops on N < r there)."""
+loop stops on N < r there).
+
+test_corr_irregular_csr gives pod_spmm_kernel what the stencil never does -- empty rows, unsorted and
+duplicate entries, column indices -1 and nh -- against the dense operator, at the same two bars (measured
+3.8e-16 at 1037 x 37 and 3.2e-16 at 517 x 130, bounds 1.9e-13 and 9.4e-14)."""
 import functools
 
 import numpy as np
@@ -162,6 +166,73 @@ def test_corr(engine, nh, ns, r, xh, dw, f32):
     print(f"C rel_fro {err:.3e}, worst-case bound {ref['bound']:.3e}")
     assert ref["bound"] < 1e-11, ref["bound"]
     assert err < 1e-10, err
+
+
+# ---- 1b. the CSR product on an operator that is not a stencil -----------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _irregular_operator(nh):
+    """A symmetric nh x nh Xh, dense (the reference) and as CSR arrays made awkward on purpose.
+
+    Dense: about 3 nh random off-diagonal pairs with values in [-1, 0); rows with i % 7 == 3 have none; the
+    diagonal is 1 + the absolute row sum, except that rows 5, 16, 27, .. have a zero diagonal -- so rows that
+    are both (38, 115, ..) are wholly empty.  Every value is rounded to fp32: the fp32 case is exact.
+    CSR: the entries of a row in shuffled order, about a third of them split into two duplicates of half the
+    value (exact), and rows with i % 5 == 0 that are not empty get two more entries with a non-zero value at
+    column -1 and column nh, which pod_spmm_kernel documents that it skips."""
+    rng = np.random.default_rng(4000 + nh)
+    f32 = lambda x: np.float64(np.float32(x))
+    X = np.zeros((nh, nh))
+    for i, j, v in zip(rng.integers(0, nh, 3 * nh), rng.integers(0, nh, 3 * nh), rng.random(3 * nh) - 1.0):
+        if i != j and i % 7 != 3 and j % 7 != 3:
+            X[i, j] = X[j, i] = f32(v)
+    for i in range(nh):
+        X[i, i] = 0.0 if i % 11 == 5 else f32(1.0 + np.abs(X[i]).sum())
+    assert np.array_equal(X, X.T) and np.array_equal(X, X.astype(np.float32).astype(np.float64))
+    rowptr, colind, val = [0], [], []
+    empty = 0
+    for i in range(nh):
+        ent = []
+        for j in np.flatnonzero(X[i]):
+            if rng.random() < 1.0 / 3.0:
+                ent += [(int(j), 0.5 * X[i, j]), (int(j), 0.5 * X[i, j])]
+            else:
+                ent.append((int(j), X[i, j]))
+        if ent and i % 5 == 0:
+            ent += [(-1, 0.75), (nh, -1.5)]
+        empty += not ent
+        for e in rng.permutation(len(ent)):
+            colind.append(ent[e][0])
+            val.append(ent[e][1])
+        rowptr.append(len(colind))
+    val = np.array(val)
+    assert empty >= 2 and np.array_equal(val, val.astype(np.float32).astype(np.float64))
+    assert any(np.any(np.diff(colind[rowptr[i]:rowptr[i + 1]]) < 0) for i in range(nh))  # unsorted rows
+    assert min(colind) == -1 and max(colind) == nh and len(colind) > np.count_nonzero(X) + 2
+    X.setflags(write=False)
+    return X, (np.array(rowptr, np.int32), np.array(colind, np.int32), val)
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+@pytest.mark.parametrize("nh,ns,r", [(1037, 37, 12), (517, 130, 16)])
+def test_corr_irregular_csr(engine, nh, ns, r, f32):
+    """pod_spmm_kernel on empty rows, unsorted and duplicate entries and out-of-range column indices, against
+    the dense operator.  Only C is compared: this Xh is not meant to be a mass matrix.  The bound below does
+    not count the fp64 sum of an operator row (at most about 15 terms here: 15 x 2^-53 more)."""
+    torch = _torch()
+    X, csr = _irregular_operator(nh)
+    S, d = _snap(nh, ns, f32), _weights(ns)
+    T = X @ S
+    Cr = (S.T @ T) * np.sqrt(np.outer(d, d))
+    Cr = 0.5 * (Cr + Cr.T)
+    bound = float(nh * 2.0 ** -53 * np.linalg.norm(np.abs(S).T @ np.abs(T)) / np.linalg.norm(S.T @ T))
+    C = engine.pod(_dev(S, f32), r, TOL, Xh=csr, d=d, svd_type=4, q=2, seed=SEED, truncate=False, return_corr=True)[3]
+    torch.cuda.synchronize()
+    assert torch.equal(C, C.t())
+    err = rel_fro(C.cpu().numpy(), Cr)
+    print(f"C (irregular CSR) rel_fro {err:.3e}, worst-case bound {bound:.3e}")
+    assert bound < 1e-11, bound
+    assert err < 1e-10, err
+    engine.sync()
 
 
 # ---- 2. parity -----------------------------------------------------------------------------------------
@@ -314,3 +385,19 @@ def test_status_codes(engine):
         engine.pod(S.half(), 4, TOL)
     # the handle still works afterwards
     assert _run(engine, 65, 1, 1)[2] in (0, 1)
+
+
+# ---- 9. a non-default stream ---------------------------------------------------------------------------------
+def test_non_default_stream(engine):
+    torch = _torch()
+    nh, ns, r = 1037, 37, 12
+    S = _dev(_snap(nh, ns, False), False)
+    ref = _run(engine, nh, ns, r, False, True, True, 4, S=S, truncate=False, return_corr=True)
+    torch.cuda.synchronize()
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        res = _run(engine, nh, ns, r, False, True, True, 4, S=S, truncate=False, return_corr=True)
+    st.synchronize()
+    for X, X0 in zip(res, ref):  # W, sigma, N, C
+        assert torch.equal(_bits(X), _bits(X0))
+    engine.sync()

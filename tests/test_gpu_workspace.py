@@ -23,6 +23,10 @@ a. test_results_do_not_depend_on_workspace: per case one sizing run, then runs o
 b. test_stale_data_of_real_runs: e512n, f32a, bLP, e512n on one handle (large LP, tiny LP, padded
    LP, large again; three dtypes) against each case run first on a fresh Engine.
 c. test_queued_runs: four runs queued with check_errors=False, one sync().
+   test_queued_calls_across_entry_points: rsvd_batched (fp64, LP 48, panels in the workspace),
+   compress_batched (fp32, LP 48, k = 17), pod (with Xh: its regions and a nested solver in the tail),
+   lowrank (slots) and the first again, queued on one handle with one sync(), each bit-equal to the same
+   call made alone; then again over every fill of the workspace.
 d. test_non_default_stream.
 e. test_inputs_are_read_only: A and Omega inside guard buffers, every byte unchanged.
 
@@ -456,6 +460,65 @@ def test_queued_runs(engine):
     for k, (cid, d) in enumerate(diffs):
         print(f"WS queued run {k} {cid}: " + ("identical" if d is None else f"differs {d}"))
     assert all(d is None for _, d in diffs), diffs
+
+
+def test_queued_calls_across_entry_points(engine):
+    """rsvd_batched, compress_batched, pod and lowrank share the handle's workspace (panel slices, POD's
+    regions with a nested solver in the tail, low-rank slots) and need very different amounts of it.  Queued
+    on one handle with nothing between them -- every input already on the device in the layout the call takes,
+    so no call copies or waits -- each must return the bits of the same call made alone, whatever the
+    workspace held before."""
+    torch = _torch()
+    import batched_cases as bc
+    import test_gpu_batched as TB
+    import test_gpu_lowrank as TL
+    import test_gpu_pod as TP
+
+    def batch(m, n, l, f32):
+        A = TB._dev_batch([TB._matrix(m, n, l, b, f32) for b in range(2)], f32)
+        om = torch.from_numpy(np.stack([TB._omega(n, l, b, f32) for b in range(2)])).to(TB._tdt(f32)).cuda()
+        return A, om.transpose(1, 2).contiguous().transpose(1, 2)
+
+    A1, om1 = batch(150, 125, 48, False)
+    assert bc.placement(150, 125, 48, 1, False) == ("f64", 48, "ws")
+    A2, om2 = batch(90, 50, 33, True)
+    nh, ns, r = 1037, 37, 12
+    Sp = TP._dev(TP._snap(nh, ns, False), False)
+    csr = tuple(torch.from_numpy(x).cuda() for x in TP._tridiag_csr(nh))
+    dw = torch.from_numpy(TP._weights(ns)).cuda()
+    Uh, Sh, Vh, Ah = TL._inputs(130, 67, TL.D, False)
+    U, V, A4 = (TL._colmajor(X, torch.float64) for X in (Uh, Vh, Ah))
+    S4 = torch.from_numpy(np.array(Sh)).cuda()
+    calls = [
+        ("rsvd_batched", lambda: engine.rsvd_batched(A1, 48, q=1, omega=om1, check_errors=False)),
+        ("compress_batched", lambda: engine.compress_batched(A2, 33, k=17, q=2, omega=om2, check_errors=False)),
+        ("pod", lambda: engine.pod(Sp, r, TP.TOL, Xh=csr, d=dw, svd_type=4, q=2, seed=TP.SEED, truncate=False,
+                                   return_corr=True)),
+        ("lowrank", lambda: engine.lowrank(U, S4, V, k=37, A=A4)),
+    ]
+    calls.append(calls[0])
+    alone = []
+    for _, call in calls[:4]:
+        torch.cuda.synchronize()
+        res = call()
+        torch.cuda.synchronize()
+        engine.sync()
+        alone.append(_host(res))
+    alone.append(alone[0])
+    assert all(np.isfinite(x).all() for res in alone for x in res)
+    ws = engine.workspace()
+    for fill in [None] + list(PATTERNS):
+        if fill is not None:
+            ws.fill_(PATTERNS[fill])
+            torch.cuda.synchronize()
+        queued = [call() for _, call in calls]
+        assert engine.workspace().data_ptr() == ws.data_ptr()  # nothing was reallocated while work was queued
+        engine.sync()
+        diffs = [(name, _first_difference(ref, _host(res))) for (name, _), ref, res in zip(calls, alone, queued)]
+        for k, (name, d) in enumerate(diffs):
+            print(f"WS queued entry points, fill {fill}, call {k} {name}: " +
+                  ("identical" if d is None else f"differs {d}"))
+        assert all(d is None for _, d in diffs), (fill, diffs)
 
 
 # ---- d. a non-default stream --------------------------------------------------------------------------
