@@ -61,6 +61,31 @@ typedef enum {
  * fp32 at the ABI. */
 typedef enum { RSVD_F64 = 0, RSVD_F32 = 1, RSVD_BF16 = 2, RSVD_FP8_E4M3 = 3 } rsvd_dtype_t;
 
+/* Dynamic range.  The reference computes in fp64 Eigen on data in physical units, and its results
+ * are equivariant under scaling: A 2^k has the singular values of A times 2^k and its singular
+ * vectors.  Guaranteed here, for every entry point and dtype: scaling A by 2^k, or passing
+ * a_scale = 2^k, scales S by 2^k and leaves U, V, the Q of rsvd_range_finder and the Q of rsvd_qr
+ * unchanged within the parity bounds of that dtype; R of rsvd_qr and C of rsvd_compress_batched /
+ * rsvd_lowrank scale by 2^k and their err2 by 2^(2k) (err2[0], a sum of exactly widened squares in
+ * a fixed order, exactly); rsvd_pod's C and sigma scale by 2^(2k) and, without the textbook flag,
+ * W by 2^-k.  This holds for sigma_max(A) up to the test matrices' (at most 16.3) and
+ *   |k| <= 40    where results are delivered in fp32 (F32, BF16, FP8_E4M3 A): the squares of all
+ *                singular values, and sums of 2^20 of them, are ordinary fp32 numbers there;
+ *   |k| <= 240   for F64 A.
+ * (tests/test_gpu_scale.py; the measured errors are tabulated in DESIGN.md §4.1.)
+ * Outside the window: where the small SVD is the one-workgroup Jacobi (rsvd_run with l <= 64 on
+ * F64 / F32 A, BF16 / FP8_E4M3 A at l <= 64, rsvd_svd's Jacobi at min(m, n) <= 64) and in the fused
+ * kernel of rsvd_run_batched / rsvd_compress_batched, a run either still meets those bounds or ends
+ * in RSVD_ERR_NUMERICAL through rsvd_sync (for a batched call also bit 1 of the matrix's info
+ * word), never in RSVD_OK with wrong numbers: a W = (Q^T A) whose largest entry lies outside
+ * 2^+-56 (fp32 Jacobi: F32 A, and the fp32 batched kernel) or 2^+-480 (fp64 Jacobi) is reported in
+ * that way (tested at 2^+-100 for an F32 rsvd_run and an fp32 batch).  The other paths (the wide
+ * engines' eigensolver and block Jacobi, rsvd_qr, rsvd_lowrank, rsvd_pod) carry no such check and
+ * have not been run outside the window: there only non-finite S is reported.
+ * Not equivariant, as in the reference, whose stop rules there are absolute: RSVD_SVD_POWER and
+ * RSVD_SVD_POWER_IC ("sigma < 1e-12"), RSVD_SVD_PARALLEL_JACOBI of rsvd_svd (pair weight
+ * max(1e-12, 1e-12 maxDiag), deno < 1e-10) and rsvd_pod's svd_type 2 where it follows that path. */
+
 /* Mirrors enum class SVDMethod { Jacobi, Power, ParallelJacobi } (include/SVD_class.hpp:28-32).
  * RSVD_SVD_POWER_IC (rsvd_run / rsvd_range_finder only) is image_compression's power-method small
  * SVD behind its 5-argument rSVD (image_compression/src/SVD.cpp:30-55, PowerMethod.cpp:3-43): B is

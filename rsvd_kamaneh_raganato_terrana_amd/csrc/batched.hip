@@ -76,11 +76,18 @@ template <> struct BEps<double> {
     static constexpr double eps = 2.220446049250313e-16;
     static constexpr double quad2 = 1e-16;
     static constexpr double lo = 1e-290, hi = 1e290;
+    // |binary exponent| of max |W| this kernel accepts, and the range of 2^-wexp in T.  Nothing here
+    // squares in T (house_factor and the projections sum in fp64), but the panels are stored in T: with
+    // max |W| at 2^-56 an entry 2^-70 below it is T = float's last normal number, and above 2^56 the
+    // rebuilt C and its squares leave little headroom.  Kept equal to jacobi.hip's Eps<>::emax so that
+    // both fp32 paths report the same window (rsvd_c.h); outside it the matrix is marked non-finite.
+    static constexpr int emax = 480, eclamp = 1000;
 };
 template <> struct BEps<float> {
     static constexpr double eps = 1.1920928955078125e-07;
     static constexpr double quad2 = 1e-8;
     static constexpr double lo = 1e-35, hi = 1e35;
+    static constexpr int emax = 56, eclamp = 120;
 };
 
 // Thread and LDS layout of the l x l area.  The Jacobi rounds use 16 threads per column pair as
@@ -105,8 +112,23 @@ struct BShape {
 };
 
 // flags[]: 0, 1 Jacobi sweep state; 2 completion candidate; 3 a reflector met a numerically zero
-// column; 4 non-finite R or S.
-constexpr int kFlDeficient = 3, kFlNonFinite = 4;
+// column; 4 non-finite R or S, or W outside the accepted range; 5 the biased binary exponent of the
+// largest |W| entry (0: W is zero).
+constexpr int kFlDeficient = 3, kFlNonFinite = 4, kFlWexp = 5;
+
+// 2^e for |e| <= 1022, assembled from its exponent field, and the e of |x| = f 2^e, f in [0.5, 1)
+__device__ __forceinline__ double pow2(int e) {
+    return __builtin_bit_cast(double, (unsigned long long)(unsigned)(1023 + e) << 52);
+}
+__device__ __forceinline__ int frexp_exp(double x) { return __builtin_amdgcn_frexp_exp(x); }
+__device__ __forceinline__ int frexp_exp(float x) { return __builtin_amdgcn_frexp_expf(x); }
+
+// The binary exponent W is divided by, from flags[kFlWexp], clamped to the range of 2^-wexp in T.
+template <typename T>
+__device__ __forceinline__ int wexp_of(const int* flags) {
+    const int w = flags[kFlWexp] ? flags[kFlWexp] - 2048 : 0;
+    return w > BEps<T>::eclamp ? BEps<T>::eclamp : (w < -BEps<T>::eclamp ? -BEps<T>::eclamp : w);
+}
 
 // Out (rows x cols, column-major ldo; column colmap[c] when given) = scale * A (rows x K, column-major
 // lda) * X (K x cols, column-major ldx).  One item = one row and 8 columns; the K sum runs in order.
@@ -261,10 +283,11 @@ __device__ __forceinline__ void brr_pair(int round, int k, int N, int& p, int& q
     }
 }
 
-// One-sided Jacobi on the columns of X (LP x LP in LDS, the l x l W in its corner, J = I), round-robin
-// pair order, the rotation and stopping rules of jacobi.hip.  Leaves the rotated columns in X, the
-// accumulated rotations in J, sig (0 for negligible or non-finite columns) and the descending rank of
-// every column.  Returns the sweeps.
+// One-sided Jacobi on the columns of X (LP x LP in LDS, the l x l W / 2^wexp in its corner -- the
+// caller's exact scaling, as jacobi.hip -- and J = I), round-robin pair order, the rotation and
+// stopping rules of jacobi.hip.  Leaves the rotated columns in X, the accumulated rotations in J, sig
+// (of the scaled W; 0 for negligible or non-finite columns) and the descending rank of every column.
+// Returns the sweeps.
 template <typename C, int LP>
 __device__ __forceinline__ int jacobi_lds(char* sm, int l) {
     typedef BShape<C, LP> SH;
@@ -571,8 +594,17 @@ __device__ void rebuild_tile(int tid, const T* Fm, int m, const T* Fn, int n, in
     __syncthreads();
 }
 
+// Waves per SIMD the register allocation must leave room for.  The instantiations below sit at exactly
+// 128 VGPRs (four waves); the handful of values the exact scaling of W adds would otherwise tip them to
+// 130 and three waves, which costs the fp32 tile shapes of tools/batched_bench.py 60 to 80 per cent.
+template <typename T, int LP, bool COMP>
+constexpr int batched_min_waves() {
+    return (!COMP && (LP == 16 || (sizeof(T) == 4 && LP <= 48))) ? 4 : 1;
+}
+
 template <typename T, int LP, bool PLDS, bool COMP>
-__global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(BatchedArgs a) {
+__global__ __launch_bounds__((BShape<T, LP>::NT)) __attribute__((amdgpu_waves_per_eu(batched_min_waves<T, LP, COMP>())))
+void batched_rsvd_kernel(BatchedArgs a) {
     typedef BShape<T, LP> SH;
     constexpr int CS = SH::CS;
     extern __shared__ __attribute__((aligned(16))) char bsm[];
@@ -599,6 +631,7 @@ __global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(Batch
         if (tid == 0) {
             flags[kFlDeficient] = 0;
             flags[kFlNonFinite] = 0;
+            flags[kFlWexp] = 0;
         }
         // Omega
         if (a.omega) {
@@ -631,15 +664,35 @@ __global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(Batch
         gemm_tn<T>(A, a.lda, m, n, Pm, m, l, Pn, n);
         __syncthreads();
         house_factor<T>(Pn, n, l, tau, scr, flags);
+        T wmax = T(0);
         for (int e = tid; e < LP * LP; e += nt) {
             const int c = e / LP, i = e % LP;
             T x = T(0);
             if (c < l && i < l && i >= c) {
                 x = Pn[c + i * n];
                 if (!isfinite(x)) flags[kFlNonFinite] = 1;  // Inf / NaN in A reach R whatever came before
+                else wmax = fmax(wmax, fabs(x));
             }
             X[c * CS + i] = x;
             J[c * CS + i] = (c == i && c < l) ? T(1) : T(0);
+        }
+        if (wmax > T(0)) atomicMax(&flags[kFlWexp], frexp_exp(wmax) + 2048);
+        __syncthreads();
+        // W / 2^wexp (jacobi.hip: the rotation test compares fourth powers of the singular values, so
+        // the sweeps run on entries of order 1 and S is scaled back below; the scaling is exact).
+        // Every thread scales the entries it stored itself.
+        // wexp is read back from LDS wherever it is needed (wexp_of), not kept in a register across
+        // the Jacobi: two more live registers cost the fp32 kernels a wave of occupancy.
+        {
+            const int wraw = flags[kFlWexp] ? flags[kFlWexp] - 2048 : 0;
+            if (tid == 0 && (wraw > BEps<T>::emax || wraw < -BEps<T>::emax)) flags[kFlNonFinite] = 1;
+            const int wexp = wexp_of<T>(flags);
+            if (wexp != 0) {
+                const T wscale = (T)pow2(-wexp);
+                int st = tid;  // (opaque, as ct below: no index of this loop is hoisted out of the loop over matrices)
+                asm volatile("" : "+v"(st));
+                for (int e = st; e < LP * LP; e += nt) X[(e / LP) * CS + e % LP] *= wscale;
+            }
         }
         __syncthreads();
         house_form_q<T>(Pn, n, l, tau);
@@ -648,7 +701,8 @@ __global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(Batch
         const bool factors = !COMP || a.U != nullptr;  // a compress call may keep them out of global memory
         if (factors) gemm_nn<T, T, T>(Pn, n, n, l, J, CS, l, Vb, a.ldv, rank, a.v_neg ? -1.0 : 1.0);
         for (int c = tid; c < l; c += nt) {
-            const T sv = (T)(sig[c] * a.s_scale);
+            const double sback = pow2(wexp_of<T>(flags));  // sig is that of W / 2^wexp
+            const T sv = (T)(sig[c] * sback * a.s_scale);
             if (!isfinite(sv)) flags[kFlNonFinite] = 1;
             if (factors) Sb[rank[c]] = sv;
         }
@@ -660,7 +714,10 @@ __global__ __launch_bounds__((BShape<T, LP>::NT)) void batched_rsvd_kernel(Batch
             // C = a_scale Pm Pn^T (|a_scale| is S's, the sign V's) against a_scale A.  tau is free after
             // the last Q: it holds the inverse of rank[].
             int* inv = reinterpret_cast<int*>(tau);
-            for (int c = tid; c < LP; c += nt) inv[rank[c]] = c;  // padding columns keep their own index
+            for (int c = tid; c < LP; c += nt) {
+                inv[rank[c]] = c;  // padding columns keep their own index
+                sig[c] *= pow2(wexp_of<T>(flags));  // the rebuild takes the singular values of W itself
+            }
             __syncthreads();
             int ct = tid;
             asm volatile("" : "+v"(ct));

@@ -216,7 +216,8 @@ int svd_jacobi_typed(rsvd_handle_t h, int64_t m, int64_t n, const T* A, int64_t 
         RSVD_CK(launch_pjacobi_ref<double>(E.R1, tall ? 1 : L.LP, tall ? L.LP : 1, tall ? 1 : -1, (int)k, L.LP, E.W, E.Uw, E.Vw, E.Sd,
                                            E.JX, h->dflags + 1, s));
     else if (L.LP <= 64)
-        RSVD_CK(launch_small_svd<double>(E.R1, (int)k, L.LP, E.Uw, E.Vw, E.Sd, h->dflags + 1, s));
+        RSVD_CK(launch_small_svd<double>(E.R1, (int)k, L.LP, E.Uw, E.Vw, E.Sd, h->dflags + 1,
+                                         h->dflags + kFlagNonFinite, s));
     else
         RSVD_CK(launch_block_jacobi<double>(E.R1, (int)k, L.LP, E.JX, E.JJ, E.Uw, E.Vw, E.Sd, E.sync, h->dflags + 1, s));
     RSVD_CK(launch_convert_scale<T>(E.Sd, S, (int)k, 1.0, s));

@@ -287,7 +287,7 @@ struct Engine {
         // Inf / NaN in A reach R through B^T = A^T Q whatever the orthonormalisations did with them
         RSVD_CK(launch_check_finite<double>(R1, L.LP * L.LP, h->dflags + kFlagNonFinite, s));
         if (d->method == RSVD_SVD_POWER || d->method == RSVD_SVD_POWER_IC) return power_stage(d, U, ldu, S, V, ldv);
-        RSVD_CK(launch_small_svd<T>(R1, L.l, L.LP, Uw, Vw, S, h->dflags + 1, s));
+        RSVD_CK(launch_small_svd<T>(R1, L.l, L.LP, Uw, Vw, S, h->dflags + 1, h->dflags + kFlagNonFinite, s));
         const double sc = std::fabs(a_scale_of(d));
         if (sc != 1.0) RSVD_CK(launch_scale_cols<T>(S, L.l, 1, L.l, sc, s));
         const int dcols = L.l;  // d = min(l, n) = l (l <= n enforced)

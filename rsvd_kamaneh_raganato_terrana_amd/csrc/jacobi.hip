@@ -67,11 +67,13 @@ template <> struct Eps<double> {
     static constexpr double eps = 2.220446049250313e-16;
     static constexpr double quad2 = 1e-16;  // (1e-8)^2: rotation ratios below 1e-8 => converged next sweep
     static constexpr double lo = 1e-290, hi = 1e290;  // safe range of d^2 + 4 g^2
+    static constexpr int emax = 480;  // |binary exponent| of max |W| the engine accepts (see below)
 };
 template <> struct Eps<float> {
     static constexpr double eps = 1.1920928955078125e-07;
     static constexpr double quad2 = 1e-8;   // (1e-4)^2
     static constexpr double lo = 1e-35, hi = 1e35;
+    static constexpr int emax = 56;
 };
 
 template <typename C> struct Two;
@@ -123,7 +125,8 @@ constexpr size_t svd_lds_bytes() {
 template <typename T, typename C, int LP>
 __global__ __launch_bounds__((JacobiShape<C, LP>::NTHR)) void small_svd_kernel(const double* __restrict__ R, int l,
                                                         double* __restrict__ Uw, double* __restrict__ Vw,
-                                                        T* __restrict__ S, int* __restrict__ info) {
+                                                        T* __restrict__ S, int* __restrict__ info,
+                                                        int* __restrict__ nonfinite) {
     typedef JacobiShape<C, LP> SH;
     constexpr int TPP = SH::TPP, CH = SH::CH, CS = SH::CS;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -138,10 +141,41 @@ __global__ __launch_bounds__((JacobiShape<C, LP>::NTHR)) void small_svd_kernel(c
     int* flags = rank + LP;                                 // [4]
     const int tid = threadIdx.x, nt = blockDim.x;
 
-    // X = W (W[i][c] = R[c][i]), J = I
-    for (int e = tid; e < LP * LP; e += nt) {
+    // The rotation test below compares fourth powers of the singular values (gg against a b, both
+    // products of squared norms), which leave fp32 for sigma outside about [1e-9, 4e9].  So W is
+    // held as W / 2^wexp, 2^wexp the power of two just above its largest entry: an exact scaling,
+    // under which every quantity of the sweeps is of order 1 whatever the magnitude of A, and S is
+    // scaled back (exactly) when it is stored.  U_w and V_w do not depend on it.
+    // R is read once, into registers (LP / 8 entries per thread); the largest |entry| goes through a
+    // wave butterfly and one LDS word per wave, so the scaling costs one barrier and no second pass.
+    constexpr int PER0 = LP * LP / SH::NTHR;
+    double rv[PER0];
+    double wmax = 0.0;
+#pragma unroll
+    for (int t = 0; t < PER0; ++t) {
+        const int e = tid + SH::NTHR * t;
         const int c = e / LP, i = e % LP;
-        X[c * CS + i] = (c < l && i < l) ? (C)R[c * LP + i] : C(0);
+        rv[t] = (c < l && i < l) ? R[c * LP + i] : 0.0;
+        wmax = fmax(wmax, fabs(rv[t]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wmax = fmax(wmax, __shfl_xor(wmax, o, 64));
+    if ((tid & 63) == 0) v[tid >> 6] = wmax;
+    __syncthreads();
+    wmax = 0.0;
+    for (int w = 0; w < SH::NTHR / 64; ++w) wmax = fmax(wmax, v[w]);
+    int wexp = 0;  // 0: W is zero (or holds nothing finite)
+    if (wmax > 0.0 && isfinite(wmax)) (void)frexp(wmax, &wexp);
+    // Outside 2^+-emax the stages in front of this kernel (Grams of squares in T) have left their
+    // range: such a run ends in RSVD_ERR_NUMERICAL, never in plausible wrong numbers.
+    if (tid == 0 && (wexp > Eps<C>::emax || wexp < -Eps<C>::emax)) atomicOr(nonfinite, 1);
+    const double wscale = ldexp(1.0, -wexp);
+    // X = W / 2^wexp (W[i][c] = R[c][i]), J = I
+#pragma unroll
+    for (int t = 0; t < PER0; ++t) {
+        const int e = tid + SH::NTHR * t;
+        const int c = e / LP, i = e % LP;
+        X[c * CS + i] = (C)(rv[t] * wscale);
         J[c * CS + i] = (c == i && c < l) ? C(1) : C(0);
     }
     const int N = (l & 1) ? l + 1 : l;       // dummy zero column when l is odd (l < LP then)
@@ -279,14 +313,15 @@ __global__ __launch_bounds__((JacobiShape<C, LP>::NTHR)) void small_svd_kernel(c
         }
         __syncthreads();
     }
-    // singular values = column norms (accumulated in fp64); negligible or non-finite -> 0 (then
-    // completed to an orthonormal U_w below)
+    // singular values = column norms (accumulated in fp64, still divided by 2^wexp); negligible
+    // -> 0 (then completed to an orthonormal U_w below); non-finite -> 0 and the sticky word
     for (int c = tid; c < LP; c += nt) {
         double s2 = 0.0;
         if (c < l)
             for (int i = 0; i < LP; ++i) s2 += (double)X[c * CS + i] * (double)X[c * CS + i];
         const double sv = sqrt(s2);
         sig[c] = (isfinite(sv) && s2 > (double)negl) ? sv : 0.0;
+        if (c < l && !isfinite(sv)) atomicOr(nonfinite, 1);
     }
     __syncthreads();
     // descending rank (stable on ties)
@@ -326,7 +361,7 @@ __global__ __launch_bounds__((JacobiShape<C, LP>::NTHR)) void small_svd_kernel(c
 #pragma unroll
     for (int t = 0; t < PER; ++t)
         if (kreg[t] >= 0) Ud[kreg[t]] = ureg[t];
-    for (int c = tid; c < l; c += nt) S[rank[c]] = (T)sig[c];
+    for (int c = tid; c < l; c += nt) S[rank[c]] = (T)ldexp(sig[c], wexp);
     __syncthreads();
     // Exactly-zero singular values (rank-deficient or zero input): complete U_w to an orthonormal
     // basis, as the reference's U (a product of rotations) always is.  For each missing column k,
@@ -388,13 +423,13 @@ __global__ __launch_bounds__((JacobiShape<C, LP>::NTHR)) void small_svd_kernel(c
 
 template <typename T>
 hipError_t launch_small_svd(const double* R, int l, int LP, double* Uw, double* Vw, T* S, int* info,
-                            hipStream_t s) {
+                            int* nonfinite, hipStream_t s) {
     typedef T C;  // compute in the panel precision: fp32 path -> fp32 Jacobi, fp64 path -> fp64
     switch (LP) {
 #define CASE(L)                                                                                              \
     case L:                                                                                                  \
         hipLaunchKernelGGL((small_svd_kernel<T, C, L>), dim3(1), dim3(JacobiShape<C, L>::NTHR), (svd_lds_bytes<C, L>()), s, R, l, Uw, Vw, \
-                           S, info);                                                                         \
+                           S, info, nonfinite);                                                              \
         break;
         CASE(16) CASE(32) CASE(48) CASE(64)
 #undef CASE
@@ -403,7 +438,9 @@ hipError_t launch_small_svd(const double* R, int l, int LP, double* Uw, double* 
     return hipGetLastError();
 }
 
-template hipError_t launch_small_svd<float>(const double*, int, int, double*, double*, float*, int*, hipStream_t);
-template hipError_t launch_small_svd<double>(const double*, int, int, double*, double*, double*, int*, hipStream_t);
+template hipError_t launch_small_svd<float>(const double*, int, int, double*, double*, float*, int*, int*,
+                                            hipStream_t);
+template hipError_t launch_small_svd<double>(const double*, int, int, double*, double*, double*, int*, int*,
+                                             hipStream_t);
 
 }  // namespace rsvd

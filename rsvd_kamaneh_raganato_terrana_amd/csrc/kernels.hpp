@@ -93,8 +93,10 @@ hipError_t launch_panel_small(const T* In, int64_t rows, int LP, const double* M
 // ---- jacobi.hip: small SVD of W = R^T (l x l) ---------------------------------------------------
 // One-sided Jacobi (round-robin order) in fp64 on one workgroup.  Outputs U_w, V_w (LP x LP
 // fp64, zero padded), S (l, descending) in the requested precision.  Returns sweeps in *info.
+// *nonfinite (the handle's sticky word) is raised when a column norm is not finite or when the
+// largest |W| entry lies outside 2^+-56 (T = float) / 2^+-480 (T = double): rsvd_c.h, dynamic range.
 template <typename T>
 hipError_t launch_small_svd(const double* R, int l, int LP, double* Uw, double* Vw, T* S, int* info,
-                            hipStream_t s);
+                            int* nonfinite, hipStream_t s);
 
 }  // namespace rsvd

@@ -598,7 +598,8 @@ struct WideEngine {
         // the small SVD always runs in fp64 (U_w, V_w feed the fp32 panel products of U and V)
         double* Sd = G;  // free scratch by now
         if (L.LP <= 64) {
-            RSVD_CK(launch_small_svd<double>(R1, L.l, L.LP, Uw, Vw, Sd, h->dflags + 1, s));
+            RSVD_CK(launch_small_svd<double>(R1, L.l, L.LP, Uw, Vw, Sd, h->dflags + 1, h->dflags + kFlagNonFinite,
+                                             s));
         } else if (sizeof(T) == 4 && eig_svd && L.l >= 3 && L.LP >= 128 && L.LP <= 512) {
             // fp32 results: G = W^T W, tridiagonalisation, multisection + inverse iteration, the
             // back-transformation, X = W V_w, then the block Jacobi's orthogonality check at the same
